@@ -19,6 +19,15 @@ Launch (driver contract):
     python bench.py --gpus N --steps K --warmup W
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line (the
+headline figure, and the roofline of the dominant kernel class from the HIP
+events sampled inside the timed steps).  `--full` adds everything that takes
+runs of its own: per-phase times and their roofline, the AR(1) layer, the
+SYRK, the large widths, the model-shaped end-to-end runs, the committed PMC
+traffic and the CPU baseline (the --no-* switches trim it).
+`--dump-outputs DIR` writes what the last timed step returned as
+DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -72,6 +81,11 @@ def parse():
     p.add_argument("--block", type=int, default=1024)
     p.add_argument("--prof-every", type=int, default=8,
                    help="sample every k-th launch of each kernel class with HIP events")
+    p.add_argument("--full", action="store_true",
+                   help="also run the extras (phases, AR(1), SYRK, large widths, end-to-end "
+                        "model shapes, CPU baseline); the --no-* switches below trim them")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's outputs to DIR/<name>.npy")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-syrk", action="store_true")
     p.add_argument("--no-large-n", action="store_true",
@@ -93,14 +107,39 @@ def make_problem(args, rank, device):
     return X, W
 
 
-def solve(g, H, W, args, gather=None):
+def solve(g, H, W, args, gather=None, keep=None):
+    """One step.  `keep`: a dict that receives everything the step's calls
+    returned (for --dump-outputs; the other steps drop them as before)."""
     R, R_x, perm = g.process_hessian_alt(H, args.eps, "energy")
     q = g.Quantizer(args.bits, args.group, args.sym)
     Wq, k = g.gptq_fwrd(W, R, q, perm, block_size=args.block, use_triton=True)
     qweight, qzeros, scales = g.pack_quantized(q)
     if gather is not None:
         gather(qweight)
+    if keep is not None:
+        keep.update(R=R, R_x=R_x, perm=perm, Wq=Wq, k=torch.tensor(k), qweight=qweight,
+                    qzeros=qzeros, scales=scales)
     return k, qweight
+
+
+DUMP_SAMPLE = 1 << 20  # elements kept of a larger output: 8 arrays stay under 64 MB
+
+
+def dump_outputs(path, outs):
+    """Write one step's outputs as path/<name>.npy: float32 for float32
+    tensors, float64 for the rest (exact for the int32 / int64 ones).  An
+    output of more than DUMP_SAMPLE elements is written as its values at
+    DUMP_SAMPLE flat indices drawn once from a fixed seed (sorted, the same
+    for every run of the same shape)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in outs.items():
+        flat = t.detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).integers(0, flat.numel(), DUMP_SAMPLE))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        dtype = torch.float32 if flat.dtype == torch.float32 else torch.float64
+        np.save(os.path.join(path, name + ".npy"), flat.to(dtype).cpu().numpy())
 
 
 def phases(g, H, W, args):
@@ -595,8 +634,9 @@ def run(args):
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        k, _ = solve(g, H, W, args, gather)
+    last = {} if args.dump_outputs and rank == 0 else None
+    for i in range(args.steps):
+        k, _ = solve(g, H, W, args, gather, last if i == args.steps - 1 else None)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -610,6 +650,9 @@ def run(args):
         dt = float(tt.item())
     ms = dt / args.steps * 1e3
     value = world * args.n * args.steps / dt
+    if last is not None:
+        dump_outputs(args.dump_outputs, last)
+        last = None
 
     # roofline of the dominant kernel class (largest estimated share of step time)
     best = None
@@ -640,18 +683,20 @@ def run(args):
                     achieved=round(achieved, 3), peak=peak, unit=unit,
                     frac=round(achieved / peak, 4), traffic=None,
                     avg_launch_ms=round(avg_ms, 5), launches_per_step=p["launches"] // args.steps)
-        roof.update(pmc_traffic(name, args))
+        if args.full:
+            roof.update(pmc_traffic(name, args))
         if name == "bulge_chase":
             roof["chain"] = bulge_chain(args.n, avg_ms)
 
-    extra = {}
-    if rank == 0:
+    # from the HIP events sampled inside the timed steps: no run of its own
+    extra = {"kernel_ms_per_step": shares} if rank == 0 else {}
+    cpu = None
+    if args.full and rank == 0:
         ph, _ = phases(g, H, W, args)
         extra["phases_ms"] = ph
         extra["spectral_path"] = phases.path
         if roof is not None:
             roof.update(phase_roofline(ph, args.n, args.m, k, args.bits))
-        extra["kernel_ms_per_step"] = shares
         if (args.n, args.m) == (4096, 4096):
             extra["ar1_rho0.9"] = ar1_solve(g, args, device)
         pm = pmc_summary(args)
@@ -663,9 +708,8 @@ def run(args):
             extra["large_n"] = large_n(g, args, device)
         if not args.no_e2e and world == 1:
             extra.update(e2e_extras(args, device))
-    cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        cpu = cpu_baseline(H, W, args)
+        if world == 1 and not args.no_cpu_baseline:
+            cpu = cpu_baseline(H, W, args)
 
     if rank == 0:
         line = {

@@ -56,8 +56,21 @@ def tiny_model(kind, seed):
     return tiny_opt(seed) if kind == "opt" else tiny_decoder(kind, seed)
 
 
+PATCHED = ("HessianAccumulator", "process_hessian_alt", "gptq_fwrd", "log_quantization_error")
+
+
+@pytest.fixture(autouse=True)
+def restore_harness(monkeypatch):
+    """_patch's stand-ins end with the test: later tests in the same process
+    (the GPU ones) run the real solver calls."""
+    import gptq_svd_amd.harness as harness
+    for name in PATCHED:
+        monkeypatch.setattr(harness, name, getattr(harness, name))
+
+
 def _patch(harness, hs):
-    """CPU stand-ins for the HIP solver calls; `hs` collects every group's H."""
+    """CPU stand-ins for the HIP solver calls (the names in PATCHED); `hs`
+    collects every group's H."""
     import sys
     sys.path.insert(0, ROOT)
     from oracle import oracle as o
@@ -175,16 +188,13 @@ def test_early_stop_matches_full_layer_passes():
 
 
 @pytest.mark.parametrize("kind", ["llama", "qwen3"])
-def test_staged_layers_match_generic(kind, monkeypatch):
+def test_staged_layers_match_generic(kind):
     """harness.quantize_model(staged=True) -- each group's calibration pass
     starts from the previous group's cached activations -- accumulates the
     same H, and produces the same weights and next-layer inputs, bit for bit,
     as re-running every layer from its input per group (staged=False).  Five
     sequences in batches of 2: a short last batch included."""
     import gptq_svd_amd.harness as harness
-    for name in ("HessianAccumulator", "process_hessian_alt", "gptq_fwrd",
-                 "log_quantization_error"):
-        monkeypatch.setattr(harness, name, getattr(harness, name))
     torch.set_num_threads(2)
     gen = torch.Generator().manual_seed(6)
     ids = [torch.randint(0, 256, (1, 16), generator=gen) for _ in range(5)]

@@ -13,7 +13,7 @@ import re
 import numpy as np
 import torch
 
-from test_dist_harness import _patch, tiny_opt
+from test_dist_harness import PATCHED, _patch, tiny_opt
 
 RUN_PATTERN = re.compile(r"INFO:\s+Params:\s+(.+)")                       # extract_log.py:19
 ERROR_PATTERN = re.compile(r"Relative prediction error:\s+([\d\.]+)")     # extract_log.py:20
@@ -43,7 +43,7 @@ def scrape(path):
 def test_run_records_parse_like_the_reference(tmp_path, monkeypatch):
     import gptq_svd_amd.harness as harness
     from oracle import oracle as o
-    for nm in ("HessianAccumulator", "process_hessian_alt", "gptq_fwrd"):
+    for nm in PATCHED:
         monkeypatch.setattr(harness, nm, getattr(harness, nm))  # restored after the test
     hs = []
     _patch(harness, hs)

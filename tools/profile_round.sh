@@ -20,11 +20,11 @@ LRE="syr2k_w|xm_kernel|syrk_compact"
 mkdir -p "$OUT"
 cd "$R"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d "$OUT/trace" -o run -- \
-  python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-large-n --no-e2e > "$OUT/trace_bench.log" 2>&1
+  python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-large-n --no-e2e > "$OUT/trace_bench.log" 2>&1
 echo "trace done"
 for C in FETCH_SIZE WRITE_SIZE; do
   timeout -k 10 300 rocprofv3 --pmc $C --kernel-include-regex "$KRE" -f csv -d "$OUT/pmc_$C" -o run -- \
-    python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-syrk --no-large-n --no-e2e > "$OUT/pmc_$C.log" 2>&1
+    python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-syrk --no-large-n --no-e2e > "$OUT/pmc_$C.log" 2>&1
   echo "pmc $C done"
 done
 N=12288 ROWS=2 REPS=1 timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d "$OUT/trace12k" -o run -- \
@@ -43,7 +43,7 @@ python3 tools/pmc_traffic.py "$OUT/pmc_traffic_n12288.json" "$(first $OUT/pmc12k
   band_update=syr2k_w band_xm=xm_kernel@xm:12288 pivot_schur=syrk_compact
 timeout -s KILL 300 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE \
   --kernel-include-regex "cross_gemm|syrk64l|dgemm8" -f csv -d "$OUT/pmc_mfma" -o run -- \
-  python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-large-n --no-e2e > "$OUT/pmc_mfma.log" 2>&1
+  python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-large-n --no-e2e > "$OUT/pmc_mfma.log" 2>&1
 echo "pmc mfma done"
 python3 tools/mfma_busy.py "$(first $OUT/pmc_mfma '*counter_collection.csv')" "$OUT/pmc_mfma_busy.json" \
   syrk64l=syrk64l cross_gemm=cross_gemm dgemm8=dgemm8
@@ -59,6 +59,6 @@ done < "$OUT/stall_passes.txt"
 python3 tools/stall_summary.py "$OUT/stall_n12288.json" band_xm=xm_kernel band_update=syr2k_w \
   pivot_schur=syrk_compact -- $(find "$OUT" -path '*stall*' -name '*counter_collection.csv' | sort)
 if [ -z "$SKIP_BENCH" ]; then  # SKIP_BENCH=1: profiles only
-  timeout -k 10 900 python3 bench.py > "$OUT/bench.log" 2>&1
+  timeout -k 10 900 python3 bench.py --full > "$OUT/bench.log" 2>&1
   tail -c 3000 "$OUT/bench.log"
 fi
