@@ -49,6 +49,9 @@ _SIGS = {
     "tg_pivoted_factor": ([_vp, _vp, _i, _vp, _i, _i, _vp, _vp, _i, _vp, _sz], _i),
     "tg_ufactor_workspace_size": ([_i, _i], _sz),
     "tg_u_factor": ([_vp, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _sz], _i),
+    "tg_u_factor_last_path": ([], _i),
+    "tg_qr_r_workspace_size": ([_i, _i], _sz),
+    "tg_qr_r": ([_vp, _vp, _i, _i, _i, _vp, _sz], _i),
     "tg_pivoted_factor_complement": ([_vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _i, _vp,
                                       _sz], _i),
     "tg_ufactor_rx_workspace_size": ([_i, _i], _sz),

@@ -79,6 +79,13 @@ bool syrk16_supported(const void *X, int n, int64_t ldx);
 hipError_t syrk16(hipStream_t st, const void *X, bool bf16, int64_t rows, int n, int64_t ldx,
                   double *H, int64_t ldh, void *ws);
 
+// Blocked Householder QR, R only (hqr.hip): the k x n row-major A (ld lda >= n,
+// 1 <= k <= n) becomes its upper-trapezoidal R in place (diagonal >= 0, strict
+// lower triangle 0).  scratch: hqr_scratch_bytes(k) bytes, 256-byte aligned.
+// Synchronises the stream once; returns 0, a hipError_t, or -99 (scratch).
+size_t hqr_scratch_bytes(int k);
+int hqr_r(hipStream_t st, double *A, int64_t lda, int k, int n, void *scratch, size_t bytes);
+
 }  // namespace tg
 
 #define TG_ARG(cond, idx, msg)                                   \

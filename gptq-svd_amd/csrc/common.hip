@@ -101,7 +101,7 @@ extern "C" int tg_profile_query(int id, double *ms, int64_t *sampled, double *by
   *total_launches = c.launches;
   return 0;
 }
-extern "C" int tg_version(void) { return 1; }
+extern "C" int tg_version(void) { return 2; }
 
 __global__ void scale_f64_kernel(const double *__restrict__ in, int64_t count, double s,
                                  double *__restrict__ out) {

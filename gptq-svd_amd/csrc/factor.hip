@@ -26,6 +26,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <type_traits>
 #include <utility>
 
@@ -1949,7 +1950,9 @@ __global__ void identity_kernel(int n, double *__restrict__ R, int64_t ldr) {
 // (max/min diag)^2 * eps puts the factor's error above ~1e-9, the factor is
 // refined by CholeskyQR passes on the explicit Q = Y R^-1 (CholeskyQR2), with
 // a shifted first factorisation when the plain one broke down (shifted
-// CholeskyQR3: G + s I, s = 11 (k^2 + k (k+1)) u ||Y||_F^2).
+// CholeskyQR3: G + s I, s = 11 (k^2 + k (k+1)) u ||Y||_F^2).  When that
+// refinement breaks down too (cond(Y) past ~3e13), R comes from a Householder
+// QR of Y itself (hqr.hip, householder_r below; switch TG_U_QR).
 // ---------------------------------------------------------------------------
 // out[0] = max |d_i|, out[1] = min d_i (0 when any is non-positive or not
 // finite), diagonal of the k x k upper factor U
@@ -2052,6 +2055,14 @@ struct RefineWs {
   double *Ri, *Q, *G, *T, *stats;
 };
 
+// Which factor the last U-factor call of this thread returned
+// (tg_u_factor_last_path): 0 Gram, 1 Gram + CholeskyQR refinement, 2 Householder.
+thread_local int g_u_path = 0;
+// refine_factor's status when the refinement gives up (as opposed to a failed
+// HIP call); the entry points return it as hipErrorUnknown
+constexpr int REFINE_BROKE = -1000;
+static int refine_status(int e) { return e == REFINE_BROKE ? int(hipErrorUnknown) : e; }
+
 // Shifted first factor: R (k x k, ld k) = chol(Y^T Y + s I), s from trace(Y^T Y).
 static int shifted_factor(hipStream_t st, const double *Y, int64_t ldy, int k, double *R,
                           RefineWs &w, double *Wb, int *info, CholStat &h) {
@@ -2072,7 +2083,7 @@ static int shifted_factor(hipStream_t st, const double *Y, int64_t ldy, int k, d
   if (h.info > 0 || !(h.dmin > 0.0)) {
     tg::set_error("U factor: shifted Cholesky of the Gram matrix broke down (%d pivots; "
                   "input not of full rank k = %d)", h.info, k);
-    return int(hipErrorUnknown);
+    return REFINE_BROKE;
   }
   return 0;
 }
@@ -2094,7 +2105,7 @@ static int cholqr_pass(hipStream_t st, const double *Y, int64_t ldy, int k, doub
   TG_HIP(read_stat(st, w.stats, info, h));
   if (h.info > 0 || !(h.dmin > 0.0)) {
     tg::set_error("U factor: CholeskyQR refinement broke down (%d pivots, k = %d)", h.info, k);
-    return int(hipErrorUnknown);
+    return REFINE_BROKE;
   }
   return 0;
 }
@@ -2117,7 +2128,53 @@ static int refine_factor(hipStream_t st, const double *Y, int64_t ldy, int k, do
   return 0;
 }
 
+// TG_U_QR (read per call): 0 auto (Gram form, Householder QR when its
+// refinement breaks down), 1 gram (no fallback), 2 householder (no Gram attempt)
+static int uqr_mode() {
+  const char *e = getenv("TG_U_QR");
+  if (e && strcmp(e, "gram") == 0) return 1;
+  if (e && strcmp(e, "householder") == 0) return 2;
+  return 0;
+}
+
+// Householder fallback (hqr.hip): Y (k x n, ld ldy) becomes its R in place.
+// No Gram matrix is formed, so cond(Y) is not squared.  The scratch is the
+// refinement's Ri .. T, contiguous in the arena and free at this point.
+static int householder_r(hipStream_t st, double *Y, int64_t ldy, int k, int n, RefineWs &w) {
+  const size_t bytes = size_t(reinterpret_cast<char *>(w.stats) - reinterpret_cast<char *>(w.Ri));
+  if (const int e = tg::hqr_r(st, Y, ldy, k, n, w.Ri, bytes)) return e;
+  hipLaunchKernelGGL(diag_range_kernel, dim3(1), dim3(256), 0, st, Y, ldy, k, w.stats);
+  TG_LAUNCHED();
+  double v[2];
+  TG_HIP(hipMemcpyAsync(v, w.stats, sizeof(v), hipMemcpyDeviceToHost, st));
+  TG_HIP(hipStreamSynchronize(st));
+  if (!(v[1] > 0.0)) {
+    tg::set_error("U factor: Householder QR broke down (zero or non-finite diagonal entry; "
+                  "input not of full rank k = %d)", k);
+    return int(hipErrorUnknown);
+  }
+  g_u_path = 2;
+  return 0;
+}
+
+// R (k x k, ld k) of Yq (k x k, ld k) at the refinement point of the R_x
+// forms: CholeskyQR refinement of the first factor in Rq, or the Householder R
+// of Yq (in place, then copied to Rq) when that breaks down or mode = 2.
+static int refine_or_householder(hipStream_t st, double *Yq, int k, double *Rq, RefineWs &rw,
+                                 double *Wb, int *info, const CholStat &h, int mode) {
+  if (mode != 2) {
+    const int e = refine_factor(st, Yq, k, k, Rq, rw, Wb, info, h);
+    if (e == 0) g_u_path = 1;
+    if (e != REFINE_BROKE || mode == 1) return refine_status(e);
+  }
+  if (const int e = householder_r(st, Yq, k, k, k, rw)) return e;
+  TG_HIP(hipMemcpyAsync(Rq, Yq, sizeof(double) * size_t(k) * k, hipMemcpyDeviceToDevice, st));
+  return 0;
+}
+
 }  // namespace
+
+extern "C" int tg_u_factor_last_path(void) { return g_u_path; }
 
 extern "C" size_t tg_pivot_workspace_size(int n, int k) {
   tg::Sizer s;
@@ -2428,32 +2485,46 @@ extern "C" int tg_u_factor(void *stream, const double *Vh, int ldv, const double
   RefineWs rw{};
   ufac_layout(ar, n, k, &A, &info, &Wb, &Rk, &rw);
   TG_WS(ar);
+  g_u_path = 0;
+  const int mode = uqr_mode();
   TG_HIP(hipMemsetAsync(info, 0, sizeof(int), st));
   hipLaunchKernelGGL(gather_scale_kernel, dim3(tg::cdiv(n, 256) < 16 ? tg::cdiv(n, 256) : 16, k),
                      dim3(256), 0, st, Vh, ldv, S, perm, n, A);
   TG_LAUNCHED();
-  // G[:k, :] = A[:, :k]^T A   (k x n) into U
-  TG_HIP(tg::dgemm(st, true, false, k, n, k, 1.0, A, n, A, n, 0.0, U, ldu));
-  TG_HIP(chol_upper_rows(st, U, ldu, k, n, Wb, info));
-  TG_HIP(zero_lower(st, U, ldu, k));
-  hipLaunchKernelGGL(diag_range_kernel, dim3(1), dim3(256), 0, st, U, int64_t(ldu), k, rw.stats);
-  TG_LAUNCHED();
-  CholStat h{};
-  TG_HIP(read_stat(st, rw.stats, info, h));
-  if (!needs_refine(h)) return 0;
-  // Refined: R11 by CholeskyQR passes on A1 = A[:, :k], then R12 = Q^T A2
-  // with the explicit Q = A1 R11^-1 (not R11^-T G12, whose error grows with
-  // cond(A1)^2).
-  if (h.info == 0 && h.dmin > 0.0)
-    TG_HIP(hipMemcpy2DAsync(Rk, sizeof(double) * k, U, sizeof(double) * ldu, sizeof(double) * k,
-                            k, hipMemcpyDeviceToDevice, st));
-  const int e = refine_factor(st, A, n, k, Rk, rw, Wb, info, h);
-  if (e != 0) return e;
-  TG_HIP(trinv(st, Rk, k, k, rw.Ri, rw.T));
-  TG_HIP(tg::dgemm(st, false, false, k, k, k, 1.0, A, n, rw.Ri, k, 0.0, rw.Q, k));
-  TG_HIP(hipMemcpy2DAsync(U, sizeof(double) * ldu, Rk, sizeof(double) * k, sizeof(double) * k, k,
+  if (mode != 2) {
+    // G[:k, :] = A[:, :k]^T A   (k x n) into U
+    TG_HIP(tg::dgemm(st, true, false, k, n, k, 1.0, A, n, A, n, 0.0, U, ldu));
+    TG_HIP(chol_upper_rows(st, U, ldu, k, n, Wb, info));
+    TG_HIP(zero_lower(st, U, ldu, k));
+    hipLaunchKernelGGL(diag_range_kernel, dim3(1), dim3(256), 0, st, U, int64_t(ldu), k, rw.stats);
+    TG_LAUNCHED();
+    CholStat h{};
+    TG_HIP(read_stat(st, rw.stats, info, h));
+    if (!needs_refine(h)) return 0;
+    // Refined: R11 by CholeskyQR passes on A1 = A[:, :k], then R12 = Q^T A2
+    // with the explicit Q = A1 R11^-1 (not R11^-T G12, whose error grows with
+    // cond(A1)^2).
+    if (h.info == 0 && h.dmin > 0.0)
+      TG_HIP(hipMemcpy2DAsync(Rk, sizeof(double) * k, U, sizeof(double) * ldu, sizeof(double) * k,
+                              k, hipMemcpyDeviceToDevice, st));
+    const int e = refine_factor(st, A, n, k, Rk, rw, Wb, info, h);
+    if (e == 0) {
+      TG_HIP(trinv(st, Rk, k, k, rw.Ri, rw.T));
+      TG_HIP(tg::dgemm(st, false, false, k, k, k, 1.0, A, n, rw.Ri, k, 0.0, rw.Q, k));
+      TG_HIP(hipMemcpy2DAsync(U, sizeof(double) * ldu, Rk, sizeof(double) * k, sizeof(double) * k,
+                              k, hipMemcpyDeviceToDevice, st));
+      if (n > k)
+        TG_HIP(tg::dgemm(st, true, false, k, n - k, k, 1.0, rw.Q, k, A + k, n, 0.0, U + k, ldu));
+      g_u_path = 1;
+      return 0;
+    }
+    if (e != REFINE_BROKE || mode == 1) return refine_status(e);
+  }
+  // Householder QR of the gathered A in place (refine_factor left it intact):
+  // the trailing columns get Q^T A2 from the reflectors themselves.
+  if (const int e = householder_r(st, A, n, k, n, rw)) return e;
+  TG_HIP(hipMemcpy2DAsync(U, sizeof(double) * ldu, A, sizeof(double) * n, sizeof(double) * n, k,
                           hipMemcpyDeviceToDevice, st));
-  if (n > k) TG_HIP(tg::dgemm(st, true, false, k, n - k, k, 1.0, rw.Q, k, A + k, n, 0.0, U + k, ldu));
   return 0;
 }
 
@@ -2590,20 +2661,23 @@ static int urx_u11_from_c(hipStream_t st, const double *Rx, int ldr, int n, int 
     return 0;
   };
   if (const int e = form_zt(true)) return e;
-  TG_HIP(tg::dsyrk_tn(st, k, k, 1.0, ZT, k, 0.0, Nm, k));         // N = Z Z^T
-  hipLaunchKernelGGL(flip_both_kernel, gk, dim3(256), 0, st, Nm, k, Rq);  // N' = J N J
-  TG_LAUNCHED();
-  TG_HIP(chol_upper_rows(st, Rq, k, k, k, Wb, info));               // N' = R^T R
-  hipLaunchKernelGGL(diag_range_kernel, dim3(1), dim3(256), 0, st, Rq, int64_t(k), k, rw.stats);
-  TG_LAUNCHED();
+  const int mode = uqr_mode();
   CholStat h{};
-  TG_HIP(read_stat(st, rw.stats, info, h));
-  if (needs_refine(h)) {
+  if (mode != 2) {
+    TG_HIP(tg::dsyrk_tn(st, k, k, 1.0, ZT, k, 0.0, Nm, k));         // N = Z Z^T
+    hipLaunchKernelGGL(flip_both_kernel, gk, dim3(256), 0, st, Nm, k, Rq);  // N' = J N J
+    TG_LAUNCHED();
+    TG_HIP(chol_upper_rows(st, Rq, k, k, k, Wb, info));               // N' = R^T R
+    hipLaunchKernelGGL(diag_range_kernel, dim3(1), dim3(256), 0, st, Rq, int64_t(k), k, rw.stats);
+    TG_LAUNCHED();
+    TG_HIP(read_stat(st, rw.stats, info, h));
+  }
+  if (mode == 2 || needs_refine(h)) {
     double *Yq = Nm;
-    TG_HIP(zero_lower(st, Rq, k, k));
+    if (mode != 2) TG_HIP(zero_lower(st, Rq, k, k));
     hipLaunchKernelGGL(flip_both_kernel, gk, dim3(256), 0, st, ZT, k, Yq);
     TG_LAUNCHED();
-    const int e = refine_factor(st, Yq, k, k, Rq, rw, Wb, info, h);
+    const int e = refine_or_householder(st, Yq, k, Rq, rw, Wb, info, h, mode);
     if (e != 0) return e;
   }
   TG_HIP(trinv(st, Rq, k, k, Yr, Tt));                              // Yr = R^-1
@@ -2627,6 +2701,8 @@ extern "C" int tg_u_factor_rx(void *stream, const double *Rx, int ldr, int n, in
   RefineWs rw{};
   urx_layout(ar, n, k, &S, &Y, &Bm, &A, &Tt, &Wb, &info, &Rq, &rw);
   TG_WS(ar);
+  g_u_path = 0;
+  const int mode = uqr_mode();
   TG_HIP(hipMemsetAsync(info, 0, sizeof(int), st));
   const bool two_chol = getenv("TG_URX_TWOCHOL") != nullptr;  // read per call (tests set it)
   if (!two_chol) {
@@ -2669,15 +2745,19 @@ extern "C" int tg_u_factor_rx(void *stream, const double *Rx, int ldr, int n, in
       if (m > 0) {
         TG_HIP(trinv_offdiag(st, Rx, ldr, Yr, k, k, Tt, TB));          // 256-block inverses
         if (const int e = trsm_upper_blocks(st, Rx, ldr, k, Rx + k, m, Yr, k, Nm, C, ldc)) return e;
-        double *V = ZT, *G = Rq;  // k x m and m x m (ld m)
-        TG_HIP(tg::dgemm(st, true, false, k, m, k, 1.0, Rx, ldr, Rx + k, ldr, 0.0, V, m));
-        TG_HIP(tg::dgemm(st, true, false, m, m, k, 1.0, Rx + k, ldr, Rx + k, ldr, 0.0, G, m));
-        TG_HIP(tg::dgemm(st, false, false, k, m, m, 0.5, C, m, G, m, 1.0, V, m));
       }
-      TG_HIP(tg::dsyrk_tn_upper(st, k, 1.0, Rx, ldr, 0.0, Nm, k));     // R11^T R11
-      if (m > 0) {
-        TG_HIP(tg::dgemm(st, false, true, k, k, m, 1.0, ZT, m, C, m, 1.0, Nm, k));  // + V C^T
-        TG_HIP(tg::dgemm(st, false, true, k, k, m, 1.0, C, m, ZT, m, 1.0, Nm, k));  // + C V^T
+      if (mode != 2) {  // N is the Gram attempt's input only
+        double *V = ZT, *G = Rq;  // k x m and m x m (ld m)
+        if (m > 0) {
+          TG_HIP(tg::dgemm(st, true, false, k, m, k, 1.0, Rx, ldr, Rx + k, ldr, 0.0, V, m));
+          TG_HIP(tg::dgemm(st, true, false, m, m, k, 1.0, Rx + k, ldr, Rx + k, ldr, 0.0, G, m));
+          TG_HIP(tg::dgemm(st, false, false, k, m, m, 0.5, C, m, G, m, 1.0, V, m));
+        }
+        TG_HIP(tg::dsyrk_tn_upper(st, k, 1.0, Rx, ldr, 0.0, Nm, k));     // R11^T R11
+        if (m > 0) {
+          TG_HIP(tg::dgemm(st, false, true, k, k, m, 1.0, ZT, m, C, m, 1.0, Nm, k));  // + V C^T
+          TG_HIP(tg::dgemm(st, false, true, k, k, m, 1.0, C, m, ZT, m, 1.0, Nm, k));  // + C V^T
+        }
       }
     } else {
       // C = R11^-1 R12 by block back substitution over 256-row blocks, as in
@@ -2699,23 +2779,26 @@ extern "C" int tg_u_factor_rx(void *stream, const double *Rx, int ldr, int n, in
         TG_HIP(tg::dgemm_upper_a(st, k, m, k, 1.0, U, ldu, C, ldc, 0.0, U + k, ldu));  // V^-1 C
       return 0;
     }
-    hipLaunchKernelGGL(flip_both_kernel, gk, dim3(256), 0, st, Nm, k, Rq);  // N' = J N J
-    TG_LAUNCHED();
-    TG_HIP(chol_upper_rows(st, Rq, k, k, k, Wb, info));               // N' = R^T R
-    hipLaunchKernelGGL(diag_range_kernel, dim3(1), dim3(256), 0, st, Rq, int64_t(k), k, rw.stats);
-    TG_LAUNCHED();
     CholStat h{};
-    TG_HIP(read_stat(st, rw.stats, info, h));
-    if (needs_refine(h)) {
-      // R is the R factor of Yq = J Z^T J (Yq^T Yq = N'): CholeskyQR passes on Yq
+    if (mode != 2) {
+      hipLaunchKernelGGL(flip_both_kernel, gk, dim3(256), 0, st, Nm, k, Rq);  // N' = J N J
+      TG_LAUNCHED();
+      TG_HIP(chol_upper_rows(st, Rq, k, k, k, Wb, info));               // N' = R^T R
+      hipLaunchKernelGGL(diag_range_kernel, dim3(1), dim3(256), 0, st, Rq, int64_t(k), k, rw.stats);
+      TG_LAUNCHED();
+      TG_HIP(read_stat(st, rw.stats, info, h));
+    }
+    if (mode == 2 || needs_refine(h)) {
+      // R is the R factor of Yq = J Z^T J (Yq^T Yq = N'): CholeskyQR passes on
+      // Yq, or its Householder QR
       double *Yq = Nm;
-      TG_HIP(zero_lower(st, Rq, k, k));
+      if (mode != 2) TG_HIP(zero_lower(st, Rq, k, k));
       if (small_m) {  // ZT held V
         if (const int e = form_zt(false)) return e;
       }
       hipLaunchKernelGGL(flip_both_kernel, gk, dim3(256), 0, st, ZT, k, Yq);
       TG_LAUNCHED();
-      const int e = refine_factor(st, Yq, k, k, Rq, rw, Wb, info, h);
+      const int e = refine_or_householder(st, Yq, k, Rq, rw, Wb, info, h, mode);
       if (e != 0) return e;
     }
     TG_HIP(trinv(st, Rq, k, k, Yr, Tt));                              // Yr = R^-1
@@ -2801,6 +2884,7 @@ extern "C" int tg_urx_u11(void *stream, const double *Rx, int ldr, int n, int k,
   RefineWs rw{};
   urx_layout(ar, n, k, &S, &Y, &Bm, &A, &Tt, &Wb, &info, &Rq, &rw);
   TG_WS(ar);
+  g_u_path = 0;
   TG_HIP(hipMemsetAsync(info, 0, sizeof(int), st));
   return urx_u11_from_c(st, Rx, ldr, n, k, C, ldc, U, ldu, Y, S, A, Rq, Tt, Wb, info, rw);
 }

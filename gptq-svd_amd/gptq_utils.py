@@ -131,6 +131,10 @@ def spectral_path(n: int, k: int, sp: SpectrumSplit) -> str:
     return "complement" if sp.nc < k and exact else "kept"
 
 
+# tg_u_factor_last_path() -> truncated_spectral_factor.last_ufactor
+_UFACTOR_PATHS = ("gram", "refined", "householder")
+
+
 def truncated_spectral_factor(H: torch.Tensor, threshold: float = 0.0005,
                               threshold_method: str = "mean_trimmed", want_rx: bool = True):
     """Native pipeline behind process_hessian_alt.  Returns (U, R_x, perm, S, k).
@@ -143,6 +147,12 @@ def truncated_spectral_factor(H: torch.Tensor, threshold: float = 0.0005,
                        rounding threshold only, H_k = H - B_c^T B_c, the same
                        pivoting, U = R(QR(S^-1 R_x)), S = R_x R_x^T
     whichever needs fewer eigenvectors.
+
+    U comes from the Cholesky factor of a Gram matrix; when that form and its
+    CholeskyQR refinement break down the library takes it from a Householder
+    QR, like the reference (gptq_utils.py:120), and ``last_ufactor`` says so
+    ("gram" | "refined" | "householder").  A breakdown of the complement
+    path's tg_u_factor_rx reruns the kept path (``last_path[0] == "kept"``).
     """
     _lib.require_cuda(H, "process_hessian_alt H")
     n = H.shape[0]
@@ -173,10 +183,12 @@ def truncated_spectral_factor(H: torch.Tensor, threshold: float = 0.0005,
         perm = torch.empty(n, dtype=torch.int64, device=dev)
         R_x = torch.empty((k, n), dtype=torch.float64, device=dev)
         U = torch.empty((k, n), dtype=torch.float64, device=dev)
-        if path == "kept":
+
+        def kept_branch():
+            nonlocal ws  # the eigensolver workspace is released before the next one is taken
             Vh = torch.empty((k, n), dtype=torch.float64, device=dev)
             call("tg_eigh_vectors", stream(), n, ptr(w), k, ptr(Vh), n, ptr(ws), ws.numel())
-            del ws
+            ws = None
             pws = workspace(_lib.lib.tg_pivot_workspace_size(n, k), dev)
             call("tg_pivoted_factor", stream(), ptr(Vh), n, ptr(S), n, k, ptr(perm), ptr(R_x),
                  n, ptr(pws), pws.numel())
@@ -184,21 +196,48 @@ def truncated_spectral_factor(H: torch.Tensor, threshold: float = 0.0005,
             uws = workspace(_lib.lib.tg_ufactor_workspace_size(n, k), dev)
             call("tg_u_factor", stream(), ptr(Vh), n, ptr(S), ptr(perm), n, k, ptr(U), n,
                  ptr(uws), uws.numel())
+
+        if path == "kept":
+            kept_branch()
         else:
             Vc = torch.empty((max(nc, 1), n), dtype=torch.float64, device=dev)
             if nc:
                 call("tg_eigh_vectors_range", stream(), n, ptr(w), k, nc, ptr(Vc), n, ptr(ws),
                      ws.numel())
-            del ws
+            ws = None
             pws = workspace(_lib.lib.tg_pivot_workspace_size(n, k), dev)
             call("tg_pivoted_factor_complement", stream(), ptr(Hd), n, ptr(Vc), n,
                  ptr(S[k:]) if nc else None, nc, n, k, ptr(perm), ptr(R_x), n, ptr(pws),
                  pws.numel())
             del pws, Vc
             uws = workspace(_lib.lib.tg_ufactor_rx_workspace_size(n, k), dev)
-            call("tg_u_factor_rx", stream(), ptr(R_x), n, n, k, ptr(U), n, ptr(uws),
-                 uws.numel())
+            try:
+                call("tg_u_factor_rx", stream(), ptr(R_x), n, n, k, ptr(U), n, ptr(uws),
+                     uws.numel())
+            except RuntimeError as err:
+                if "broke down" not in str(err):
+                    raise
+                # The complement form's C = R11^-1 R12 stages have no Householder
+                # form: rerun the kept branch from a fresh copy of Hd.  This costs
+                # a second eigensolve on a path that was fatal before; keeping
+                # the eigensolver workspace alive on every call instead would
+                # raise the default path's peak memory.
+                logging.warning(" complement-path U factor broke down (%s); rerunning the "
+                                "kept path", err)
+                del uws
+                path = "kept"
+                A = Hd.clone()
+                ws = workspace(_lib.lib.tg_eigh_workspace_size(n), dev)
+                w = torch.empty(n, dtype=torch.float64, device=dev)
+                call("tg_eigh_values", stream(), ptr(A), n, n, ptr(w), ptr(ws), ws.numel())
+                del A
+                kept_branch()
         truncated_spectral_factor.last_path = (path, nc)
+        ufac = _UFACTOR_PATHS[_lib.lib.tg_u_factor_last_path()]
+        truncated_spectral_factor.last_ufactor = ufac
+        if ufac == "householder":
+            logging.warning(" U factor: the Gram form broke down or was switched off; "
+                            "Householder QR used (n = %d, k = %d)", n, k)
     return U, (R_x if want_rx else None), perm, S, k
 
 

@@ -124,6 +124,29 @@ size_t tg_ufactor_workspace_size(int n, int k);
 int tg_u_factor(void *stream, const double *Vh, int ldv, const double *S, const int64_t *perm,
                 int n, int k, double *U, int ldu, void *ws, size_t ws_bytes);
 
+/* Which factor the calling thread's last tg_u_factor / tg_u_factor_rx /
+ * tg_urx_u11 call returned: 0 the Gram-form (Cholesky) factor, 1 the Gram form
+ * with CholeskyQR refinement, 2 the Householder QR below.  The Gram form
+ * squares the condition number; when its shifted CholeskyQR3 refinement breaks
+ * down, the factor is taken from a Householder QR instead, as the reference
+ * does throughout (gptq_utils.py:120).  TG_U_QR (read per call) = auto
+ * (default) | gram (no fallback: the breakdown is returned as an error) |
+ * householder (no Gram attempt). */
+int tg_u_factor_last_path(void);
+
+/* Blocked Householder QR, R only (the QR of gptq_utils.py:120 without Q):
+ * A (k x n row-major, 1 <= k <= n, ld lda >= n) becomes its upper-trapezoidal
+ * R in place: strict lower triangle exactly 0, rows sign-flipped so the
+ * diagonal is >= 0, columns n .. lda-1 untouched.  Communication-avoiding
+ * (TSQR-tree) panels of 32 columns, trailing update by FP64 MFMA (hqr.hip);
+ * deterministic.  Column norms are scaled (as dnrm2), so squares neither
+ * overflow nor underflow.  Synchronises the stream once, at the end, to read
+ * the breakdown word: a non-finite column norm, or a non-finite entry of the
+ * finished R (which a NaN / Inf anywhere in A leaves), returns hipErrorUnknown
+ * with a "broke down" message. */
+size_t tg_qr_r_workspace_size(int k, int n);
+int tg_qr_r(void *stream, double *A, int lda, int k, int n, void *ws, size_t ws_bytes);
+
 /* ---- A4/A5 complement path (same outputs, no kept eigenvectors) ----------
  * When the dropped eigenpairs above rounding level are fewer than the kept
  * ones (k > n/2, the usual case: Qwen3-8B keeps ~99.5%), H_k = H - B_c^T B_c
