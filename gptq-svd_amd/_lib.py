@@ -74,6 +74,10 @@ _SIGS = {
     "tg_pred_error": ([_vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _sz], _i),
     "tg_pack_codes": ([_vp, _vp, _i, _i, _i, _vp], _i),
     "tg_pack_zeros": ([_vp, _vp, _i, _i, _i, _i, _vp], _i),
+    "tg_dequant_packed": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _i64], _i),
+    "tg_qgemm_workspace_size": ([_i, _i, _i], _sz),
+    "tg_qgemm": ([_vp, _vp, _i, _i, _i64, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _i,
+                  _i64, _vp, _sz], _i),
 }
 
 EXPORTED = []

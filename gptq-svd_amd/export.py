@@ -16,6 +16,9 @@ bits / group_size / sym / desc_act=false / static_groups=true and the
 TruncGPTQ settings and per-layer ranks.  Dequantisation:
 W[:, j] = (code_u[:, j] - zero_u[:, g(j)]) * scale[:, g(j)], with symmetric
 codes stored +2^(b-1) (so zero_u = 2^(b-1)).
+
+``load_quantized`` is the way back: it puts the packed tensors into
+``qlinear.QuantLinear`` modules of a model, which run them without unpacking.
 """
 from __future__ import annotations
 
@@ -25,7 +28,7 @@ from typing import Any, Dict, Optional
 
 import torch
 
-__all__ = ["save_quantized", "read_quantized"]
+__all__ = ["save_quantized", "read_quantized", "load_quantized"]
 
 
 def save_quantized(path: str, model: torch.nn.Module, packed: Dict[str, Dict[str, torch.Tensor]],
@@ -75,9 +78,80 @@ def save_quantized(path: str, model: torch.nn.Module, packed: Dict[str, Dict[str
 
 def read_quantized(path: str):
     """(tensors dict, quantize_config dict) of a checkpoint written by
-    save_quantized (plain reads; unpacking lives with the consumer)."""
+    save_quantized (plain reads; the consumer is load_quantized / qlinear)."""
     from safetensors.torch import load_file
     tensors = load_file(os.path.join(path, "model.safetensors"))
     with open(os.path.join(path, "quantize_config.json")) as f:
         qc = json.load(f)
     return tensors, qc
+
+
+def _set_submodule(model: torch.nn.Module, name: str, new: torch.nn.Module) -> None:
+    parent_name, _, leaf = name.rpartition(".")
+    parent = model.get_submodule(parent_name) if parent_name else model
+    setattr(parent, leaf, new)
+
+
+def load_quantized(model: torch.nn.Module, path: str, device=None) -> torch.nn.Module:
+    """Load a checkpoint written by save_quantized into `model` (the dense
+    architecture, any weights) and return it: every ``nn.Linear`` whose
+    ``<name>.qweight`` is in the checkpoint becomes a ``qlinear.QuantLinear``
+    holding the packed tensors (bias kept, in the linear's dtype); every other
+    tensor is loaded as is.  ``quantize_config.json`` must be a static-group
+    ``desc_act=false`` configuration with supported bits, and every ``g_idx``
+    must be the trivial ``arange(in) // group`` map (act-order checkpoints are
+    out of scope).  `device`: where the model is moved (default: it stays)."""
+    from .qlinear import QuantLinear
+    tensors, qc = read_quantized(path)
+    bits, group = int(qc["bits"]), int(qc["group_size"])
+    if bits not in (2, 3, 4, 8):
+        raise ValueError(f"quantize_config.json: bits={bits} is not one of 2, 3, 4, 8")
+    if qc.get("desc_act", False):
+        raise ValueError("quantize_config.json: desc_act=true (act-order) checkpoints are not "
+                         "supported")
+    if not isinstance(qc.get("sym"), bool):
+        raise ValueError("quantize_config.json: sym must be true or false")
+    fmt = qc.get("checkpoint_format", "gptq_v2")
+    if fmt != "gptq_v2":
+        raise ValueError(f"quantize_config.json: checkpoint_format={fmt!r}; only gptq_v2 (true "
+                         "zero points) is supported")
+    names = [k[:-len(".qweight")] for k in tensors if k.endswith(".qweight")]
+    used = set()
+    for name in names:
+        try:
+            lin = model.get_submodule(name)
+        except AttributeError:
+            raise KeyError(f"{name}: packed in the checkpoint but absent from the model") from None
+        if not isinstance(lin, torch.nn.Linear):
+            raise TypeError(f"{name}: expected nn.Linear, found {type(lin).__name__}")
+        keys = {k: f"{name}.{k}" for k in ("qweight", "qzeros", "scales", "g_idx", "bias")}
+        for k in ("qzeros", "scales", "g_idx"):
+            if keys[k] not in tensors:
+                raise KeyError(f"{keys[k]} is missing from the checkpoint")
+        bias = tensors.get(keys["bias"])
+        if (bias is None) != (lin.bias is None):
+            raise ValueError(f"{name}: the checkpoint and the model disagree about a bias")
+        if bias is not None:
+            bias = bias.to(lin.bias.dtype)
+        try:
+            q = QuantLinear.from_packed(tensors[keys["qweight"]], tensors[keys["qzeros"]],
+                                        tensors[keys["scales"]], bits, group, bias=bias,
+                                        g_idx=tensors[keys["g_idx"]], device=lin.weight.device)
+        except ValueError as e:
+            raise ValueError(f"{name}: {e}") from None
+        if (q.out_features, q.in_features) != (lin.out_features, lin.in_features):
+            raise ValueError(f"{name}: packed weight is {q.out_features} x {q.in_features}, the "
+                             f"model's linear is {lin.out_features} x {lin.in_features}")
+        _set_submodule(model, name, q)
+        used.update(v for v in keys.values() if v in tensors)
+    rest = {k: v for k, v in tensors.items() if k not in used}
+    missing, unexpected = model.load_state_dict(rest, strict=False)
+    missing = [k for k in missing if k not in used]
+    if unexpected:
+        raise KeyError(f"checkpoint tensors without a place in the model: {sorted(unexpected)}")
+    if missing:
+        # tied parameters are saved once per name, so nothing should be missing
+        raise KeyError(f"model tensors missing from the checkpoint: {sorted(missing)}")
+    if device is not None:
+        model.to(device)
+    return model

@@ -570,15 +570,22 @@ def quantize_model(model: nn.Module, input_ids_list: Sequence[torch.Tensor], mod
 
 def run_and_record(model: nn.Module, input_ids_list: Sequence[torch.Tensor], save_path: str,
                    run_config: Optional[Dict[str, Any]] = None, evaluate=None,
-                   **kw) -> Dict[str, Any]:
+                   evaluate_packed=None, **kw) -> Dict[str, Any]:
     """``quantize_model`` with the reference's run records (quantize.py:48-66,
     :254-284): ``<save_path>/quantization.log`` receives every log line of the
     run in the reference's format and ``<save_path>/results.json`` the config,
     the per-module ``layer_stats`` and the metrics.  ``evaluate`` (optional):
     a callable ``model -> ppl`` run after quantisation (e.g.
     ``evaluate.evaluate_perplexity`` bound to a tokenizer); its value becomes
-    ``metrics.quantized_ppl`` as at quantize.py:281.  In multi-GPU mode only
-    rank 0 writes the files; every rank runs the same quantisation."""
+    ``metrics.quantized_ppl`` as at quantize.py:281.  ``evaluate_packed``
+    (optional, opt-in): a callable ``model -> ppl`` run on the artefact a user
+    ships instead of the dense model: the run packs (``pack=True`` is implied),
+    writes the checkpoint to ``<save_path>/packed`` with
+    ``export.save_quantized``, loads it back with ``export.load_quantized``
+    into a copy of the model (fp16 when the model is fp32: the packed kernels
+    take 16-bit activations) and records the value as ``metrics.packed_ppl``.
+    In multi-GPU mode only rank 0 writes the files and evaluates the packed
+    copy; every rank runs the same quantisation."""
     from . import runlog
     input_ids_list = list(input_ids_list)
     world, rank = _world(kw.get("pg"))
@@ -595,6 +602,8 @@ def run_and_record(model: nn.Module, input_ids_list: Sequence[torch.Tensor], sav
     if mid:
         cfg["model_id"] = mid
     cfg.update(run_config or {})
+    if evaluate_packed is not None:
+        kw["pack"] = True
     if rank != 0:
         res = quantize_model(model, input_ids_list, **kw)
         if evaluate is not None:
@@ -606,5 +615,26 @@ def run_and_record(model: nn.Module, input_ids_list: Sequence[torch.Tensor], sav
         if evaluate is not None:
             runlog.substep("Running final evaluation...")
             ppl = float(evaluate(model))
-        rl.finish(res["layer_stats"], res["total_time"], ppl)
+        packed_ppl = None
+        if evaluate_packed is not None:
+            runlog.substep("Evaluating the packed checkpoint...")
+            packed_ppl = float(evaluate_packed(_packed_copy(model, res, save_path, kw)))
+        rl.finish(res["layer_stats"], res["total_time"], ppl, packed_ppl)
     return res
+
+
+def _packed_copy(model: nn.Module, res: Dict[str, Any], save_path: str,
+                 kw: Dict[str, Any]) -> nn.Module:
+    """Save the run's packed checkpoint under ``<save_path>/packed`` and load
+    it into a 16-bit copy of `model`."""
+    import copy
+    import os
+    from .export import load_quantized, save_quantized
+    path = os.path.join(save_path, "packed")
+    save_quantized(path, model, res["packed"], int(kw.get("w_bits", 4)),
+                   int(kw.get("group_size", -1)), bool(kw.get("sym", False)),
+                   extra_config={"mode": kw.get("mode", "eigh")})
+    twin = copy.deepcopy(model)
+    if next(twin.parameters()).dtype == torch.float32:
+        twin = twin.half()
+    return load_quantized(twin, path).eval()

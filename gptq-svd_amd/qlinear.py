@@ -1,0 +1,164 @@
+"""Packed-weight inference (A14): the consumer of the checkpoint that
+``export.save_quantized`` writes.
+
+``dequantize_packed`` decodes the AutoGPTQ ``gptq_v2`` tensors back into the
+dense weight (``tg_dequant_packed``); ``QuantLinear`` keeps them packed and
+runs ``y = x W^T + bias`` straight from the packed words (``tg_qgemm``: a
+split-K GEMV for up to 16 rows, an MFMA tile kernel above).  Both are HIP
+kernels; there is no CPU or eager fallback.
+
+Layout (export.py): ``qweight`` int32 (in*b/32, out), ``qzeros`` int32
+(G, out*b/32), ``scales`` fp16 or fp32 (G, out), ``g_idx`` int32 (in,) -- only
+the trivial map ``arange(in) // group`` (static groups, original column
+order).  w = (code_u - zero_u) * scale.
+"""
+from __future__ import annotations
+
+from typing import Optional
+
+import torch
+from torch import nn
+
+from ._lib import DTYPES, call, lib, ptr, require_cuda, stream, workspace
+
+__all__ = ["QuantLinear", "dequantize_packed"]
+
+_BITS = (2, 3, 4, 8)
+
+
+def _shapes(qweight: torch.Tensor, qzeros: torch.Tensor, scales: torch.Tensor, w_bits: int,
+            group_size: int):
+    """(m, n, g) of a packed triple, checked against each other."""
+    if w_bits not in _BITS:
+        raise ValueError(f"w_bits must be one of {_BITS}, got {w_bits}")
+    if qweight.dtype != torch.int32 or qzeros.dtype != torch.int32:
+        raise ValueError("qweight and qzeros must be int32")
+    if scales.dtype not in (torch.float16, torch.float32):
+        raise ValueError("scales must be float16 or float32")
+    nw, m = qweight.shape
+    if (nw * 32) % w_bits:
+        raise ValueError(f"qweight has {nw} word rows, not a whole number of {w_bits}-bit values")
+    n = nw * 32 // w_bits
+    g = group_size if group_size > 0 else n
+    if n % g:
+        raise ValueError(f"group_size {group_size} does not divide in_features {n}")
+    G = n // g
+    if tuple(scales.shape) != (G, m) or tuple(qzeros.shape) != (G, m * w_bits // 32):
+        raise ValueError(f"packed shapes disagree: qweight {tuple(qweight.shape)}, qzeros "
+                         f"{tuple(qzeros.shape)}, scales {tuple(scales.shape)} for bits={w_bits}, "
+                         f"group={group_size}")
+    return m, n, g
+
+
+def dequantize_packed(qweight: torch.Tensor, qzeros: torch.Tensor, scales: torch.Tensor,
+                      w_bits: int, group_size: int,
+                      dtype: torch.dtype = torch.float16) -> torch.Tensor:
+    """Dense weight (out, in) of `dtype` (fp16 / bf16 / fp32):
+    ``float(code_u - zero_u) * float(scale)`` rounded once to `dtype`."""
+    m, n, g = _shapes(qweight, qzeros, scales, w_bits, group_size)
+    for t, what in ((qweight, "qweight"), (qzeros, "qzeros"), (scales, "scales")):
+        require_cuda(t, what)
+    if dtype not in (torch.float16, torch.bfloat16, torch.float32):
+        raise ValueError(f"dtype must be float16, bfloat16 or float32, got {dtype}")
+    dev = qweight.device
+    qweight, qzeros, scales = qweight.contiguous(), qzeros.contiguous(), scales.contiguous()
+    out = torch.empty((m, n), dtype=dtype, device=dev)
+    with torch.cuda.device(dev):
+        call("tg_dequant_packed", stream(), ptr(qweight), ptr(qzeros), ptr(scales),
+             DTYPES[scales.dtype], m, n, g, w_bits, ptr(out), DTYPES[dtype], n)
+    return out
+
+
+class QuantLinear(nn.Module):
+    """A linear layer whose weight stays packed.  The buffer names are the
+    checkpoint's keys, so ``load_state_dict`` fills it.  ``module.to(dtype)``
+    converts floating buffers like any module: fp32 ``scales`` become 16-bit
+    with it (and the decoded weight changes accordingly)."""
+
+    def __init__(self, in_features: int, out_features: int, w_bits: int, group_size: int,
+                 bias: bool = False, scale_dtype: torch.dtype = torch.float16,
+                 bias_dtype: torch.dtype = torch.float16, device=None):
+        super().__init__()
+        if w_bits not in _BITS:
+            raise ValueError(f"w_bits must be one of {_BITS}, got {w_bits}")
+        g = group_size if group_size > 0 else in_features
+        if in_features % 32 or g % 32 or in_features % g or (out_features * w_bits) % 32:
+            raise ValueError(
+                f"QuantLinear needs in_features % 32 == 0, group % 32 == 0 dividing in_features "
+                f"and out_features * bits % 32 == 0 (got in={in_features}, out={out_features}, "
+                f"group={group_size}, bits={w_bits})")
+        self.in_features, self.out_features = int(in_features), int(out_features)
+        self.w_bits, self.group_size = int(w_bits), int(group_size)
+        G = in_features // g
+        self.register_buffer("qweight", torch.zeros((in_features * w_bits // 32, out_features),
+                                                    dtype=torch.int32, device=device))
+        self.register_buffer("qzeros", torch.zeros((G, out_features * w_bits // 32),
+                                                   dtype=torch.int32, device=device))
+        self.register_buffer("scales", torch.zeros((G, out_features), dtype=scale_dtype,
+                                                   device=device))
+        self.register_buffer("g_idx", (torch.arange(in_features, dtype=torch.int32,
+                                                    device=device) // g).to(torch.int32))
+        if bias:
+            self.register_buffer("bias", torch.zeros(out_features, dtype=bias_dtype, device=device))
+        else:
+            self.bias = None
+
+    @classmethod
+    def from_packed(cls, qweight: torch.Tensor, qzeros: torch.Tensor, scales: torch.Tensor,
+                    w_bits: int, group_size: int, bias: Optional[torch.Tensor] = None,
+                    g_idx: Optional[torch.Tensor] = None, device=None) -> "QuantLinear":
+        """From the packed tensors (a checkpoint's, or ``pack_quantized``'s).
+        `g_idx`, when given, must be the trivial ``arange(in) // group``."""
+        m, n, g = _shapes(qweight, qzeros, scales, w_bits, group_size)
+        if g_idx is not None:
+            triv = torch.arange(n, dtype=torch.int64) // g
+            if tuple(g_idx.shape) != (n,) or not torch.equal(g_idx.cpu().to(torch.int64), triv):
+                raise ValueError("g_idx is not the static arange(in_features) // group_size map "
+                                 "(act-order checkpoints are not supported)")
+        dev = device if device is not None else qweight.device
+        q = cls(n, m, w_bits, group_size, bias=bias is not None, scale_dtype=scales.dtype,
+                bias_dtype=bias.dtype if bias is not None else torch.float16, device=dev)
+        q.qweight.copy_(qweight)
+        q.qzeros.copy_(qzeros)
+        q.scales.copy_(scales)
+        if bias is not None:
+            q.bias.copy_(bias.detach())
+        return q
+
+    def extra_repr(self) -> str:
+        return (f"in_features={self.in_features}, out_features={self.out_features}, "
+                f"bits={self.w_bits}, group_size={self.group_size}, bias={self.bias is not None}")
+
+    def dequantize(self, dtype: torch.dtype = torch.float16) -> torch.Tensor:
+        """The dense (out, in) weight."""
+        return dequantize_packed(self.qweight, self.qzeros, self.scales, self.w_bits,
+                                 self.group_size, dtype)
+
+    @torch.no_grad()
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        require_cuda(x, "QuantLinear input")
+        require_cuda(self.qweight, "QuantLinear.qweight")
+        if x.dtype not in (torch.float16, torch.bfloat16):
+            raise RuntimeError(f"QuantLinear takes float16 or bfloat16 activations, got {x.dtype} "
+                               "(there is no fp32 kernel and no fallback)")
+        if x.shape[-1] != self.in_features:
+            raise RuntimeError(f"QuantLinear: last dim {x.shape[-1]} != in_features "
+                               f"{self.in_features}")
+        n, m = self.in_features, self.out_features
+        x2 = x.reshape(-1, n)
+        T = x2.shape[0]
+        y = torch.empty((T, m), dtype=x.dtype, device=x.device)
+        if T > 0:
+            if x2.stride(1) != 1 or (T > 1 and x2.stride(0) < n):
+                x2 = x2.contiguous()
+            ldx = x2.stride(0) if T > 1 else n
+            bias = self.bias
+            with torch.cuda.device(x.device):
+                nbytes = lib.tg_qgemm_workspace_size(T, m, n)
+                ws = workspace(nbytes, x.device)
+                call("tg_qgemm", stream(), ptr(x2), DTYPES[x.dtype], T, ldx, ptr(self.qweight),
+                     ptr(self.qzeros), ptr(self.scales), DTYPES[self.scales.dtype], m, n,
+                     self.group_size, self.w_bits, ptr(bias),
+                     DTYPES[bias.dtype] if bias is not None else 0, ptr(y), DTYPES[x.dtype], m,
+                     ptr(ws), nbytes)
+        return y.reshape(*x.shape[:-1], m)

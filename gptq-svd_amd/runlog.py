@@ -85,13 +85,17 @@ class RunLog:
         return self
 
     def finish(self, layer_stats: List[Dict[str, Any]], total_time: float,
-               quantized_ppl: Optional[float] = None) -> Dict[str, Any]:
+               quantized_ppl: Optional[float] = None,
+               packed_ppl: Optional[float] = None) -> Dict[str, Any]:
         header("COMPLETED")                                           # quantize.py:254-256
         logging.info(f"Total processing time: {total_time / 60:.2f} minutes")
         metrics: Dict[str, Any] = {"total_time": total_time}
         if quantized_ppl is not None:                                 # quantize.py:279-281
             logging.info(f"Final Quantized PPL: {quantized_ppl:.4f}")
             metrics["quantized_ppl"] = quantized_ppl
+        if packed_ppl is not None:      # this build's packed-checkpoint evaluation (opt-in)
+            logging.info(f"Packed checkpoint PPL: {packed_ppl:.4f}")
+            metrics["packed_ppl"] = packed_ppl
         log = {"config": self.config, "layer_stats": list(layer_stats), "metrics": metrics}
         with open(os.path.join(self.save_path, "results.json"), "w") as f:
             json.dump(log, f, indent=4)

@@ -248,6 +248,51 @@ int tg_pack_codes(void *stream, const uint8_t *codes, int m, int n, int w_bits, 
 int tg_pack_zeros(void *stream, const float *zero, int m, int G, int w_bits, int sym,
                   int32_t *qzeros);
 
+/* ---- A14: packed inference (absent in the reference) ----------------------
+ * The consumer of the A13 layout.  qweight int32 (n*b/32 x m): value i of
+ * output feature r occupies bits [i*b, i*b+b) of the little-endian stream of
+ * column r; qzeros int32 (G x m*b/32): the same stream along the output
+ * features; scales (G x m) of scale_dtype TG_F16 or TG_F32; G = n/g with
+ * g = group, or n when group <= 0; b in {2, 3, 4, 8}.  Codes and zeros are
+ * stored in offset form, so sym and asym decode alike:
+ * w = (code_u - zero_u) * scale.
+ *
+ * tg_dequant_packed: out (m x n, ld ldo, original column order) of out_dtype
+ * TG_F16 / TG_BF16 / TG_F32.  Numerics: float(code_u - zero_u) * float(scale),
+ * one fp32 multiply of an exact integer, then one round-to-nearest-even to
+ * out_dtype, so a host computation reproduces it bit for bit.  Requires
+ * (n*b) % 32 == 0, (m*b) % 32 == 0 and g dividing n. */
+int tg_dequant_packed(void *stream, const int32_t *qweight, const int32_t *qzeros,
+                      const void *scales, int scale_dtype, int m, int n, int group, int w_bits,
+                      void *out, int out_dtype, int64_t ldo);
+
+/* tg_qgemm: Y (T x m, ld ldy) = X (T x n, ld ldx) * W^T (+ bias), x_dtype
+ * TG_F16 or TG_BF16, y_dtype = x_dtype or TG_F32, bias (m, nullable) of
+ * bias_dtype TG_F16 / TG_BF16 / TG_F32.  Numerics: the weight operand is
+ * exactly tg_dequant_packed's output with out_dtype = x_dtype; products and
+ * sums are fp32; the bias is added in fp32; one rounding to y_dtype.  The
+ * result is bit-identical from call to call (no atomics).
+ * Requires n % 32 == 0, g % 32 == 0 and (m*b) % 32 == 0; anything else is
+ * rejected with the argument index before any device work.
+ * Two regimes.  gemv (T <= 16; chosen up to T = 4): 64 output features per
+ * workgroup, K split over S workgroups of at most 512 values each.  mfma (any
+ * T; chosen above): an MFMA tile kernel that unpacks 128-value K slabs of its
+ * (64 or 128 rows) x 64 features tile into LDS; it splits K as well (S splits
+ * of at least 512 values) while the output tiles alone are fewer than ~512
+ * workgroups.  With S > 1 the partial sums [S][T][m] fp32 go to the workspace
+ * and a second kernel adds them in ascending split order, then the bias; with
+ * S = 1 the MFMA kernel writes Y itself.  The environment variable TG_QGEMM =
+ * auto | gemv | mfma (read per call) forces a regime; gemv with T > 16 is an
+ * argument error (-4).
+ * tg_qgemm_workspace_size(T, m, n): S*T*m*4 bytes (+ alignment slack) for the
+ * larger S of the regimes that take T (at m = n = 4096: S = 16 for T <= 16,
+ * 8 at T = 64, and 0 bytes once the tiles fill the device, e.g. T = 4096). */
+size_t tg_qgemm_workspace_size(int T, int m, int n);
+int tg_qgemm(void *stream, const void *X, int x_dtype, int T, int64_t ldx, const int32_t *qweight,
+             const int32_t *qzeros, const void *scales, int scale_dtype, int m, int n, int group,
+             int w_bits, const void *bias, int bias_dtype, void *Y, int y_dtype, int64_t ldy,
+             void *ws, size_t ws_bytes);
+
 #ifdef __cplusplus
 }
 #endif
