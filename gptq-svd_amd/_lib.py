@@ -33,6 +33,8 @@ _SIGS = {
     "tg_syrk_workspace_size": ([_i], _sz),
     "tg_syrk_accum_ws": ([_vp, _vp, _i, _i64, _i, _i64, _vp, _i, _vp, _sz], _i),
     "tg_scale_f64": ([_vp, _vp, _i64, _d, _vp], _i),
+    "tg_sketch_omega": ([_vp, ctypes.c_uint64, _i64, _i, _i64, _vp, _i64], _i),
+    "tg_sketch_accum": ([_vp, _vp, _i, _i64, _i, _i64, ctypes.c_uint64, _i64, _vp, _i, _i64], _i),
     "tg_profile_enable": ([_i, _i], _i),
     "tg_profile_reset": ([], _i),
     "tg_profile_query": ([_i, ctypes.POINTER(_d), ctypes.POINTER(_i64), ctypes.POINTER(_d),

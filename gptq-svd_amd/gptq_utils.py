@@ -5,7 +5,7 @@ Mirrors the names, argument meaning and error behaviour of
 (``quantize.py:14``) only has to change its import line:
 
     from gptq_svd_amd.gptq_utils import (gptq_fwrd, Quantizer, process_hessian_alt,
-                                         HessianAccumulator)
+                                         HessianAccumulator, Sketcher, process_sketch)
 
 Every numerical stage runs in the HIP library (``libtruncgptq.so``, C ABI in
 ``include/truncgptq.h``) on the caller's current HIP stream; torch provides
@@ -27,7 +27,7 @@ from ._lib import call, ptr, stream, workspace
 __all__ = [
     "HessianAccumulator", "process_hessian_alt", "process_hessian", "Quantizer", "gptq_fwrd",
     "triton_process_block", "log_quantization_error", "next_power_of_2",
-    "truncated_spectral_factor", "pack_quantized",
+    "truncated_spectral_factor", "pack_quantized", "Sketcher", "process_sketch",
 ]
 
 
@@ -136,7 +136,8 @@ _UFACTOR_PATHS = ("gram", "refined", "householder")
 
 
 def truncated_spectral_factor(H: torch.Tensor, threshold: float = 0.0005,
-                              threshold_method: str = "mean_trimmed", want_rx: bool = True):
+                              threshold_method: str = "mean_trimmed", want_rx: bool = True,
+                              min_rank: int = 0):
     """Native pipeline behind process_hessian_alt.  Returns (U, R_x, perm, S, k).
 
     eigh (two-stage reduction + bisection) -> rank rule -> then either
@@ -153,6 +154,8 @@ def truncated_spectral_factor(H: torch.Tensor, threshold: float = 0.0005,
     QR, like the reference (gptq_utils.py:120), and ``last_ufactor`` says so
     ("gram" | "refined" | "householder").  A breakdown of the complement
     path's tg_u_factor_rx reruns the kept path (``last_path[0] == "kept"``).
+    ``min_rank`` clamps the rule's rank from below (process_sketch keeps at
+    least one direction, gptq_utils.py:65); the default raises on rank 0.
     """
     _lib.require_cuda(H, "process_hessian_alt H")
     n = H.shape[0]
@@ -172,7 +175,7 @@ def truncated_spectral_factor(H: torch.Tensor, threshold: float = 0.0005,
         # one host sync for the rank and the spectrum split (the reference syncs
         # here too, gptq_utils.py:100, :106)
         wk = torch.cat((w, kdev.to(torch.float64))).cpu().numpy()
-        k = int(wk[n])
+        k = max(int(wk[n]), min(int(min_rank), n))
         if k < 1:
             raise RuntimeError("process_hessian_alt: truncation rank is 0 "
                                "(threshold keeps no eigenvalue)")
@@ -239,6 +242,128 @@ def truncated_spectral_factor(H: torch.Tensor, threshold: float = 0.0005,
             logging.warning(" U factor: the Gram form broke down or was switched off; "
                             "Householder QR used (n = %d, k = %d)", n, k)
     return U, (R_x if want_rx else None), perm, S, k
+
+
+# ---------------------------------------------------------------------------
+# A1s  sketch mode  (gptq_utils.py:33-84, :171-211)
+# ---------------------------------------------------------------------------
+class Sketcher:
+    """Y += Omega x with a Gaussian Omega (rank x tokens) that is generated
+    inside the GEMM kernel and never stored (tg_sketch_accum; the reference
+    draws a torch.randn of rank x tokens per hook call and calls addmm_,
+    gptq_utils.py:196-200).
+
+    Omega is a pure function of (seed, sketch row, global token index)
+    (include/truncgptq.h), so Y does not depend on how the calibration tokens
+    are split into batches, and the same seed reproduces Y bit for bit.
+    ``seed=None`` draws one 63-bit seed from torch's default CPU generator at
+    construction, so ``torch.manual_seed`` governs a run as it does in the
+    reference.  fp16 / bf16 / fp32 inputs go straight into the kernel; other
+    dtypes are cast to fp32 (the reference casts everything)."""
+
+    def __init__(self, layer, rank: int, device="cuda", seed: Optional[int] = None):
+        self.layer = layer
+        self.rank = int(rank)
+        self.device = device
+        self.in_features = layer.in_features
+        if self.rank < 1:
+            raise ValueError(f"Sketcher: rank must be positive, got {rank}")
+        self.Y = torch.zeros((self.rank, self.in_features), device=device, dtype=torch.float32)
+        _lib.require_cuda(self.Y, "Sketcher device")
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+        self.seed = int(seed) & (2 ** 64 - 1)
+        self.n_samples = 0
+
+    def hook_fn(self, module, input_args, output):            # gptq_utils.py:184-202
+        x = input_args[0]
+        if x.dim() > 2:
+            x = x.reshape(-1, x.shape[-1])
+        if x.shape[0] == 0:
+            return
+        self.add_batch(x)
+
+    def add_batch(self, x):
+        """The harness's accumulator interface (HessianAccumulator.add_batch)."""
+        if x.dim() > 2:
+            x = x.reshape(-1, x.shape[-1])
+        _lib.require_cuda(x, "Sketcher input")
+        if x.dtype not in (torch.float16, torch.bfloat16, torch.float32):
+            x = x.to(torch.float32)
+        if x.stride(-1) != 1:
+            x = x.contiguous()
+        rows, n = x.shape
+        if n != self.in_features:
+            raise RuntimeError(f"Sketcher: expected {self.in_features} features, got {n}")
+        if rows == 0:
+            return
+        with torch.cuda.device(self.Y.device):
+            call("tg_sketch_accum", stream(), ptr(x), _lib.DTYPES[x.dtype], rows, n, x.stride(0),
+                 self.seed, self.n_samples, ptr(self.Y), self.rank, self.Y.stride(0))
+        self.n_samples += rows
+
+    def get_scaled_sketch(self):                              # gptq_utils.py:204-211
+        if self.n_samples == 0:
+            return None, None, 0
+        self.Y.mul_(1.0 / float(np.sqrt(float(self.n_samples) * float(self.rank))))
+        return self.Y
+
+
+def process_sketch(sketch: torch.Tensor, threshold: float = 1e-2,
+                   threshold_method: str = "mean_trimmed"
+                   ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(R, perm) like gptq_utils.py:33-84: R float64 k x n upper trapezoidal with
+    positive diagonal, perm int64.
+
+    Gram route.  The reference takes the singular values S and right vectors
+    Vh of the sketch Y from geqrf followed by svd(R); these are the eigenpairs
+    (S^2, Vh) of G = Y^T Y.  Here G is formed in float64 from the fp32 sketch
+    (tg_syrk_accum: products and sums in float64) and the eigh pipeline of
+    process_hessian_alt does the rest: S = sqrt(max(eigenvalue, 1e-12)), the
+    same rank rules on S, the pivot order of diag(S_k) Vh_k and R = R(QR(diag(1/S_k) Vh_k
+    P)), with the rank clamped to at least 1 (gptq_utils.py:65).  Squaring
+    costs nothing the thresholds keep: a kept singular value is within about
+    1e-2 of the reference value S[1:33].mean() (mean_trimmed) or carries part
+    of 1 - eps of the energy, so its square stands 1e-4 .. 1e-8 below the
+    largest eigenvalue, far above float64 rounding (1e-16 n).  Checked on the
+    CPU against the QR + SVD route on four synthetic sketches (ar1 n=256 rank
+    512 mean_trimmed 1e-2; lognormal n=256 rank 1024 energy 1e-4; gaussian
+    n=384 rank 384 mean_trimmed 1e-2; ar1 n=512 rank 512 from 300 tokens,
+    rank-deficient with k=291, energy 1e-4): the same k, an identical perm,
+    and R within 4e-14 .. 9e-13 relative.
+
+    One difference from the reference's rules: the pipeline's clamp
+    S >= 1e-6 (process_hessian_alt's, gptq_utils.py:94) is absent from the
+    reference's process_sketch.  Null or rounding-level directions therefore
+    sit at S = 1e-6 here instead of ~1e-7 S[0]; mean_trimmed keeps them where
+    the reference drops them only if threshold * S[1:33].mean() < 1e-6, i.e.
+    for a scaled sketch of order 1e-4 or smaller at threshold 1e-2 (the
+    activations themselves that small), and the energy rule counts 1e-12 per
+    such direction.  Sketches of ordinary scale are unaffected: the
+    rank-deficient goldens (k = 290 of 512 under energy, k = 150 of 256 under
+    mean_trimmed) give the reference's k.
+
+    The reference's CPU round trip of the sketch (:40-46) is memory juggling
+    and is not reproduced.  An unknown ``threshold_method`` raises ValueError
+    (the reference hits a NameError there)."""
+    if threshold_method not in ("energy", "mean_trimmed"):
+        raise ValueError(f"process_sketch: unknown threshold_method {threshold_method!r}")
+    _lib.require_cuda(sketch, "process_sketch sketch")
+    if sketch.dim() != 2:
+        raise RuntimeError("process_sketch: the sketch must be rank x in_features")
+    Y = sketch.to(torch.float32)
+    if Y.stride(-1) != 1:
+        Y = Y.contiguous()
+    rank, n = Y.shape
+    G = torch.zeros((n, n), dtype=torch.float64, device=Y.device)
+    with torch.cuda.device(Y.device):
+        call("tg_syrk_accum", stream(), ptr(Y), _lib.TG_F32, rank, n, Y.stride(0), ptr(G), n)
+    try:
+        U, _, perm, _, _ = truncated_spectral_factor(G, threshold, threshold_method,
+                                                     want_rx=False, min_rank=1)
+    finally:
+        del G
+    return U, perm
 
 
 def process_hessian_alt(H: torch.Tensor, threshold: float = 0.0005,

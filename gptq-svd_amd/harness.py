@@ -6,7 +6,8 @@ The reference's data flow is kept exactly: capture the inputs of the first
 decoder layer; for each layer and each sequenced group (q/k/v -> o ->
 gate/up -> down), hook the group's first linear, run every calibration batch
 through the layer to accumulate H (FP64 MFMA SYRK), factorise once per group
-(``process_hessian_alt`` for "eigh", ``process_hessian`` for "gptq"),
+(``process_hessian_alt`` for "eigh", ``process_hessian`` for "gptq"; mode
+"svd" accumulates a Gaussian sketch instead of H and calls ``process_sketch``),
 quantize each linear of the group with ``gptq_fwrd`` (block 1024) and write
 the dequantised weight back; then re-run the calibration batches through the
 quantised layer to produce the next layer's inputs.
@@ -55,8 +56,9 @@ import torch
 from torch import nn
 
 from . import dist as tgdist
-from .gptq_utils import (HessianAccumulator, Quantizer, gptq_fwrd, log_quantization_error,
-                         pack_quantized, process_hessian, process_hessian_alt)
+from .gptq_utils import (HessianAccumulator, Quantizer, Sketcher, gptq_fwrd,
+                         log_quantization_error, pack_quantized, process_hessian,
+                         process_hessian_alt, process_sketch)
 
 __all__ = ["get_layers", "get_sequenced_groups", "capture_initial_inputs", "quantize_model",
            "adaptive_eps", "StageClock", "check_factor_agrees", "run_and_record"]
@@ -322,11 +324,21 @@ def quantize_model(model: nn.Module, input_ids_list: Sequence[torch.Tensor], mod
                    pack: bool = False, offload: bool = False, pg=None, early_stop: bool = True,
                    clock: Optional[StageClock] = None, save_path: Optional[str] = None,
                    run_config: Optional[Dict[str, Any]] = None,
-                   staged: Optional[bool] = None) -> Dict[str, Any]:
+                   staged: Optional[bool] = None, sketch_ratio: float = 4.0,
+                   sketch_seed: Optional[int] = None) -> Dict[str, Any]:
     """Quantise every sequenced linear of `model` in place (layer by layer).
 
     mode "eigh" = TruncGPTQ (process_hessian_alt + gptq_fwrd(use_triton=True));
-    mode "gptq" = the GPTQ comparator (process_hessian + use_triton=False).
+    mode "gptq" = the GPTQ comparator (process_hessian + use_triton=False);
+    mode "svd" = the reference's default (quantize.py:122-125, :154-167): no H is
+    formed; each group accumulates a Gaussian sketch of rank
+    int(in_features * sketch_ratio) (``Sketcher``, the fused HIP sketch GEMM),
+    ``process_sketch`` gives (R, perm) and gptq_fwrd(use_triton=True) quantises.
+    `sketch_seed`: every group's Sketcher takes this seed (the sketch is then
+    the same function of the tokens in every run and for every batch size);
+    None draws each Sketcher's seed from torch's default CPU generator, so
+    ``torch.manual_seed`` governs the run as in the reference.  Single-process
+    only (sharded sketches are not implemented).
     `offload`: move each layer to `device` for its turn and back to the CPU
     afterwards (the reference's policy, quantize.py:101, :239); by default
     the model stays where it is (a whole 8B/70B model fits in 288 GB).
@@ -352,8 +364,10 @@ def quantize_model(model: nn.Module, input_ids_list: Sequence[torch.Tensor], mod
     when the caller evaluates afterwards (see ``run_and_record``).
     Returns {"layer_stats": [...], "total_time": s, "packed": {name: tensors}}.
     """
-    if mode not in ("eigh", "gptq"):
-        raise ValueError(f"mode must be 'eigh' or 'gptq', got {mode!r}")
+    if mode not in ("eigh", "gptq", "svd"):
+        raise ValueError(f"mode must be 'eigh', 'gptq' or 'svd', got {mode!r}")
+    if mode == "svd" and _world(pg)[0] > 1:
+        raise ValueError("mode 'svd' is single-process")
     if save_path is not None:
         res = run_and_record(model, input_ids_list, save_path, run_config, mode=mode,
                              w_bits=w_bits, group_size=group_size, sym=sym, eps=eps,
@@ -361,7 +375,7 @@ def quantize_model(model: nn.Module, input_ids_list: Sequence[torch.Tensor], mod
                              damp_percent=damp_percent, use_adaptive_eps=use_adaptive_eps,
                              batch_size=batch_size, device=device, block_size=block_size,
                              pack=pack, offload=offload, pg=pg, early_stop=early_stop, clock=clock,
-                             staged=staged)
+                             staged=staged, sketch_ratio=sketch_ratio, sketch_seed=sketch_seed)
         return res
     t_start = time.time()
     world, rank = _world(pg)
@@ -412,23 +426,37 @@ def quantize_model(model: nn.Module, input_ids_list: Sequence[torch.Tensor], mod
                 raise _Stop
         return hook
 
+    def new_accumulator(first):
+        """The group's accumulator: H (eigh, gptq) or the sketch Y (svd); both
+        take the group's inputs through add_batch."""
+        in_features = first.weight.shape[1]
+        if mode == "svd":
+            return Sketcher(first, int(in_features * sketch_ratio), device=device,
+                            seed=sketch_seed)
+        return HessianAccumulator(in_features, device=device)
+
     def solve_group(i, layer, names, acc):
         """All-reduce, factorise and quantise one sequenced group."""
         cur_eps = adaptive_eps(names[0], eps) if use_adaptive_eps else eps
         ev = clock.start() if clock else None
-        allreduce_hessian(acc, pg)
+        if mode != "svd":
+            allreduce_hessian(acc, pg)
         if clock and world > 1:
             clock.stop("allreduce", ev)
             ev = clock.start()
-        H = acc.get_hessian()
-        if mode == "eigh":
+        H = acc.get_scaled_sketch() if mode == "svd" else acc.get_hessian()
+        if mode == "svd":
+            logging.info(f"   Processing Sketch (Shape: {tuple(H.shape)})")
+            R, perm = process_sketch(H, threshold=cur_eps, threshold_method=threshold_method)
+            R_x = None
+        elif mode == "eigh":
             R, R_x, perm = process_hessian_alt(H, threshold=cur_eps,
                                                threshold_method=threshold_method)
         else:
             R, perm = process_hessian(H, actorder=actorder, damp_percent=damp_percent)
             R_x = None
         if clock:
-            clock.stop(f"factor_n{H.shape[0]}", ev)
+            clock.stop(f"factor_n{H.shape[1]}", ev)
         del H
         if world > 1:
             check_factor_agrees(R, perm, pg)
@@ -440,19 +468,19 @@ def quantize_model(model: nn.Module, input_ids_list: Sequence[torch.Tensor], mod
             if world > 1:
                 W = sub.weight.data.float()
                 Wq, k, q = quantize_linear_sharded(W, R, perm, w_bits, group_size, sym,
-                                                   block_size, mode == "eigh", pg)
+                                                   block_size, mode != "gptq", pg)
                 if R_x is not None and rank == 0:
                     log_quantization_error(W, Wq, R_x, perm)
             else:
                 Wq, k = gptq_fwrd(sub.weight.data.float(), R, q, perm,
-                                  block_size=block_size, use_triton=(mode == "eigh"), R_x=R_x)
+                                  block_size=block_size, use_triton=(mode != "gptq"), R_x=R_x)
             sub.weight.copy_(Wq)
             full = f"layer_{i}.{name}"
             if pack:
                 qw, qz, sc = pack_quantized(q)
                 packed[qual.get(id(sub), full)] = dict(qweight=qw, qzeros=qz, scales=sc)
             dt = time.time() - t0
-            used = k if mode == "eigh" else "N/A"
+            used = k if mode != "gptq" else "N/A"
             logging.info(f"   {name: <15} | Rank: {str(used): <4} | Time: {dt:.2f}s")
             stats.append({"name": full, "rank": used, "time": dt})
         if clock:
@@ -475,7 +503,7 @@ def quantize_model(model: nn.Module, input_ids_list: Sequence[torch.Tensor], mod
         for gi, names in enumerate(get_sequenced_groups(layer)):
             logging.info(f"[Layer {i + 1}/{len(layers)}] Group {gi + 1}: {', '.join(names)}")
             first = _submodule(layer, names[0])
-            acc = HessianAccumulator(first.weight.shape[1], device=device)
+            acc = new_accumulator(first)
             hook = first.register_forward_pre_hook(accumulate(acc), with_kwargs=True)
             ev = clock.start() if clock else None
             try:
@@ -511,7 +539,7 @@ def quantize_model(model: nn.Module, input_ids_list: Sequence[torch.Tensor], mod
 
         for gi, names in enumerate(groups):
             logging.info(f"[Layer {i + 1}/{len(layers)}] Group {gi + 1}: {', '.join(names)}")
-            acc = HessianAccumulator(_submodule(layer, names[0]).weight.shape[1], device=device)
+            acc = new_accumulator(_submodule(layer, names[0]))
             ev = clock.start() if clock else None
             for bi, (j, x, kwb) in enumerate(batches()):
                 if gi == 0:
@@ -594,10 +622,15 @@ def run_and_record(model: nn.Module, input_ids_list: Sequence[torch.Tensor], sav
         seq_len=int(input_ids_list[0].shape[-1]) if len(input_ids_list) else 0,
         batch_size=kw.get("batch_size", 8), w_bits=kw.get("w_bits", 4),
         group_size=kw.get("group_size", -1), sym=bool(kw.get("sym", False)),
-        eps=kw.get("eps", 1e-2), mode=kw.get("mode", "eigh"),
+        eps=kw.get("eps", 1e-2), sketch_ratio=float(kw.get("sketch_ratio", 4.0)),
+        mode=kw.get("mode", "eigh"),
         threshold_method=kw.get("threshold_method", "mean_trimmed"),
         actorder=bool(kw.get("actorder", False)), damp_percent=kw.get("damp_percent", 0.01),
         adaptive_eps=bool(kw.get("use_adaptive_eps", False)), save_path=save_path, no_save=True)
+    if kw.get("mode") == "svd":
+        # what makes a sketch-mode run reproducible (None: every Sketcher drew its
+        # seed from torch's default CPU generator, i.e. torch.manual_seed governs)
+        cfg["sketch_seed"] = kw.get("sketch_seed")
     mid = getattr(getattr(model, "config", None), "_name_or_path", None)
     if mid:
         cfg["model_id"] = mid

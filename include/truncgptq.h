@@ -66,6 +66,47 @@ int tg_syrk_accum_ws(void *stream, const void *X, int x_dtype, int64_t rows, int
  * out may alias H. */
 int tg_scale_f64(void *stream, const double *H, int64_t count, double inv_n, double *out);
 
+/* ---- A1s: Gaussian sketch accumulation -----------------------------------
+ * Replaces Sketcher.hook_fn (gptq_utils.py:184-202): `R = torch.randn(rank,
+ * tokens)` followed by `Y.addmm_(R, x.float())`.  Here Omega is generated
+ * inside the GEMM kernel and never stored.  Contract:
+ *
+ * omega is a pure function of (seed, r, g), r the sketch row and g = t0 + t
+ * the global token index; nothing else (tile, launch shape, rank, T) enters.
+ *   Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) and counter
+ *   (g & 0xffffffff, g >> 32, (r >> 7) * 32 + (r & 31), 0).  Its outputs
+ *   x0..x3 serve the four rows that differ only in j = (r >> 5) & 3, by
+ *   Box-Muller on the pairs (x0, x1) -> j = 0, 1 and (x2, x3) -> j = 2, 3:
+ *   u1 = ((xa >> 8) + 1) * 2^-24 in (0, 1] (the log never sees 0),
+ *   u2 = (xb >> 8) * 2^-24 in [0, 1), rad = sqrtf(-2 logf(u1)),
+ *   omega = rad * cos(2 pi u2) for the even j, rad * sin(2 pi u2) for the odd
+ *   (fp32; cospif / sinpif of the exact 2 u2).
+ * tg_sketch_omega and tg_sketch_accum call the same device function, so the
+ * values they use are bit-identical.
+ *
+ * Each Y[r, c] is one fp32 fused-multiply-add chain in ascending t that starts
+ * from the value already in Y:
+ *   acc = Y[r, c];  acc = fmaf(omega(seed, r, t0 + t), float(X[t, c]), acc),
+ *   t = 0 .. T-1
+ * (v_mfma_f32_32x32x2_f32 with the accumulator loaded from Y; the conversion
+ * of X to fp32 is exact).  No split over tokens, no atomics, no workspace; K
+ * padding multiplies zero by zero.  Hence, bitwise: one call over T tokens
+ * equals any split of the same tokens into consecutive calls with advancing
+ * t0, and rows 0..r1-1 of a rank-r2 sketch equal the rank-r1 sketch.
+ * Columns n .. ldy-1 of Y are not touched.
+ *
+ * Omega[r][t] (rank x T fp32, ld ldo) = omega(seed, r, t0 + t).  Tests / tools
+ * only (rank <= 65535). */
+int tg_sketch_omega(void *stream, uint64_t seed, int64_t t0, int rank, int64_t T,
+                    float *Omega, int64_t ldo);
+/* Y (rank x n fp32, ld ldy) += Omega(seed; rows 0..rank-1, tokens t0..t0+T-1) * X,
+ * X (T x n, ld ldx) of x_dtype TG_F16 / TG_BF16 / TG_F32.  T = 0 is a no-op.
+ * Limits (rejected with the argument index): ldy < 2^21, because a workgroup
+ * addresses its 512-row tile of Y with 32-bit offsets (-11); rank <= 65535 *
+ * 512 (-10); t0 >= 0 and t0 + T <= INT64_MAX (-8, -4). */
+int tg_sketch_accum(void *stream, const void *X, int x_dtype, int64_t T, int n, int64_t ldx,
+                    uint64_t seed, int64_t t0, float *Y, int rank, int64_t ldy);
+
 /* FP64 MFMA GEMM used by every dense stage (exported for tests / reuse):
  * C = alpha op(A) op(B) + beta C, row-major, op(A) M x K, op(B) K x N.
  * Hand-written kernels only (gemm64.hip: 8-wave 128 x 128 tiles for large
