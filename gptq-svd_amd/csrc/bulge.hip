@@ -1915,7 +1915,8 @@ extern "C" int tg_band_tridiag(void *stream, const double *A, int n, int lda, do
   TG_ARG(A != nullptr, 2, "A is null");
   TG_ARG(n >= 1, 3, "n must be >= 1");
   TG_ARG(lda >= n, 4, "lda < n");
-  TG_ARG(d != nullptr && e != nullptr, 5, "d / e is null");
+  TG_ARG(d != nullptr, 5, "d is null");
+  TG_ARG(e != nullptr, 6, "e is null");
   hipStream_t st = static_cast<hipStream_t>(stream);
   tg::Arena ar(ws, ws_bytes);
   BandWs b{};

@@ -1829,7 +1829,9 @@ extern "C" int tg_truncation_rank(void *stream, const double *w_asc, int n, doub
                                   int rule, double *S_desc, int32_t *k_dev) {
   TG_ARG(w_asc, 2, "null w");
   TG_ARG(n >= 1, 3, "n < 1");
-  TG_ARG(S_desc && k_dev, 6, "null output");
+  TG_ARG(rule >= TG_RULE_NONE && rule <= TG_RULE_MEAN_TRIMMED, 5, "unknown rank rule");
+  TG_ARG(S_desc, 6, "null S_desc");
+  TG_ARG(k_dev, 7, "null k_dev");
   if (n <= RANK_LDS_N) {
     const size_t lds = sizeof(double) * size_t(n);
     if (lds > 48 * 1024)
@@ -1847,6 +1849,11 @@ extern "C" int tg_truncation_rank(void *stream, const double *w_asc, int n, doub
 
 extern "C" int tg_eigh_vectors(void *stream, int n, const double *w_asc, int k, double *Vh, int ldv,
                                void *ws, size_t ws_bytes) {
+  TG_ARG(n >= 1, 2, "n < 1");
+  TG_ARG(w_asc, 3, "null w");
+  TG_ARG(k >= 1 && k <= n, 4, "k must be in [1, n]");
+  TG_ARG(Vh, 5, "null Vh");
+  TG_ARG(ldv >= n, 6, "ldv < n");
   return tg_eigh_vectors_range(stream, n, w_asc, 0, k, Vh, ldv, ws, ws_bytes);
 }
 

@@ -2401,13 +2401,13 @@ extern "C" int tg_pivoted_factor_complement(void *stream, const double *H, int l
                                             int n, int k, int64_t *perm, double *Rx, int ldr,
                                             void *ws, size_t ws_bytes) {
   TG_ARG(H, 2, "null H");
+  TG_ARG(n >= 1, 8, "n < 1");
+  TG_ARG(k >= 1 && k <= n, 9, "k must be in [1, n]");
   TG_ARG(ldh >= n, 3, "ldh < n");
+  TG_ARG(nc >= 0 && nc <= k && k + nc <= n, 7, "nc must be in [0, min(k, n - k)]");
   TG_ARG(nc == 0 || Vc, 4, "null Vc");
   TG_ARG(nc == 0 || ldvc >= n, 5, "ldvc < n");
   TG_ARG(nc == 0 || Sc, 6, "null Sc");
-  TG_ARG(nc >= 0 && nc <= k && k + nc <= n, 7, "nc must be in [0, min(k, n - k)]");
-  TG_ARG(n >= 1, 8, "n < 1");
-  TG_ARG(k >= 1 && k <= n, 9, "k must be in [1, n]");
   TG_ARG(perm, 10, "null perm");
   TG_ARG(!Rx || ldr >= n, 12, "ldr < n");
   hipStream_t st = (hipStream_t)stream;
@@ -2853,7 +2853,8 @@ extern "C" int tg_urx_c(void *stream, const double *Rx, int ldr, int n, int k, i
   TG_ARG(Rx, 2, "null Rx");
   TG_ARG(ldr >= n, 3, "ldr < n");
   TG_ARG(k >= 1 && k <= n, 5, "k must be in [1, n]");
-  TG_ARG(c0 >= 0 && c0 <= c1 && c1 <= n - k, 6, "column range outside [0, n - k]");
+  TG_ARG(c0 >= 0 && c0 <= c1, 6, "c0 must be in [0, c1]");
+  TG_ARG(c1 <= n - k, 7, "c1 > n - k");
   TG_ARG(C || c1 == c0, 8, "null C");
   TG_ARG(ldc >= c1 - c0, 9, "ldc < c1 - c0");
   hipStream_t st = (hipStream_t)stream;
@@ -2895,8 +2896,10 @@ extern "C" int tg_urx_u12(void *stream, const double *U, int ldu, int k, const d
   TG_ARG(ldu >= k, 3, "ldu < k");
   TG_ARG(k >= 1, 4, "k < 1");
   TG_ARG(ncols >= 0, 7, "ncols < 0");
-  TG_ARG((C && out) || ncols == 0, 5, "null C / out");
-  TG_ARG(ldc >= ncols && ldo >= ncols, 6, "ldc / ldo < ncols");
+  TG_ARG(C || ncols == 0, 5, "null C");
+  TG_ARG(out || ncols == 0, 8, "null out");
+  TG_ARG(ldc >= ncols, 6, "ldc < ncols");
+  TG_ARG(ldo >= ncols, 9, "ldo < ncols");
   if (ncols == 0) return 0;
   TG_HIP(tg::dgemm_upper_a((hipStream_t)stream, k, ncols, k, 1.0, U, ldu, C, ldc, 0.0, out, ldo));
   return 0;

@@ -745,6 +745,9 @@ extern "C" int tg_dgemm(void *stream, int transA, int transB, int M, int N, int 
                         double *C, int ldc) {
   TG_ARG(M >= 0 && N >= 0 && K >= 0, 4, "negative size");
   TG_ARG(A && B && C, 8, "null pointer");
+  TG_ARG(lda >= (transA ? M : K), 9, "lda < columns of A as stored");
+  TG_ARG(ldb >= (transB ? K : N), 11, "ldb < columns of B as stored");
+  TG_ARG(ldc >= N, 14, "ldc < N");
   TG_HIP(tg::dgemm((hipStream_t)stream, transA != 0, transB != 0, M, N, K, alpha, A, lda, B, ldb,
                    beta, C, ldc));
   return 0;

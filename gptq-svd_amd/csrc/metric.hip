@@ -214,7 +214,8 @@ extern "C" size_t tg_pred_error_workspace_size(int m, int n, int k) {
 extern "C" int tg_pred_error(void *stream, const float *W, const float *Wq, int m, int n, int ldw,
                              const double *Rx, int k, int ldr, const int64_t *perm, double *out,
                              void *ws, size_t ws_bytes) {
-  TG_ARG(W && Wq, 2, "null W / Wq");
+  TG_ARG(W, 2, "null W");
+  TG_ARG(Wq, 3, "null Wq");
   TG_ARG(m >= 1, 4, "m < 1");
   TG_ARG(n >= 1, 5, "n < 1");
   TG_ARG(ldw >= n, 6, "ldw < n");

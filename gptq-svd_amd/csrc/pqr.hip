@@ -158,7 +158,8 @@ __device__ __forceinline__ void load_row(const PqrArgs &g, int i, double (&x)[32
   const int ic = min(i, g.m - 1);
   const double *s = g.A + (g.r0 + int64_t(ic)) * g.lda + g.p;
   double2 v[16];
-  if ((g.lda & 1) == 0 && (g.p & 1) == 0) {
+  // 16-byte loads need an aligned base as well as an even stride and column
+  if ((g.lda & 1) == 0 && (g.p & 1) == 0 && (reinterpret_cast<uintptr_t>(g.A) & 15) == 0) {
     const double2 *s2 = reinterpret_cast<const double2 *>(s);
 #pragma unroll
     for (int l = 0; l < 16; ++l) v[l] = s2[l];

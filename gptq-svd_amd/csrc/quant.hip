@@ -621,6 +621,8 @@ size_t block_smem(int bw, bool dbl = true) {
 bool block_dbl(int m) { return tg::cdiv(m, RW) <= tg::xcd_info().xcds * tg::xcd_info().cus_per_xcd; }
 
 constexpr int MAX_BLOCK = 2048;
+// the packed layout exists for these widths only (include/truncgptq.h, A13 / A14)
+bool pack_bits_ok(int b) { return b == 2 || b == 3 || b == 4 || b == 8; }
 
 hipError_t ensure_block_smem() {
   static bool done = false;  // per-process; attribute is per function, device-independent
@@ -650,7 +652,8 @@ extern "C" int tg_group_params(void *stream, const float *W, int m, int n, int l
   const int g = group > 0 ? group : n;
   TG_ARG(n % g == 0, 6, "n % group_size != 0 (gptq_utils.py:253)");
   TG_ARG(w_bits >= 2 && w_bits <= 8, 7, "w_bits must be in [2, 8]");
-  TG_ARG(scale && zero, 9, "null output");
+  TG_ARG(scale, 9, "null scale");
+  TG_ARG(zero, 10, "null zero");
   const int G = n / g;
   const float maxq = sym ? float((1 << (w_bits - 1)) - 1) : float((1 << w_bits) - 1);
   const int64_t waves = int64_t(m) * G;
@@ -664,10 +667,20 @@ extern "C" int tg_process_block(void *stream, const float *w, int ldw, const flo
                                 const float *z, int ldz, const float *R, int ldr, int m, int B,
                                 int minq, int maxq, float *q, int ldq, float *e, int lde,
                                 void *ws, size_t ws_bytes) {
-  TG_ARG(w && s && z && R, 2, "null input");
+  TG_ARG(w, 2, "null w");
+  TG_ARG(s, 4, "null s");
+  TG_ARG(z, 6, "null z");
+  TG_ARG(R, 8, "null R");
   TG_ARG(m > 0, 10, "m <= 0");
   TG_ARG(B > 0 && B <= MAX_BLOCK, 11, "block width must be in [1, 2048]");
-  TG_ARG(q && e, 14, "null output");
+  TG_ARG(ldw >= B, 3, "ldw < B");
+  TG_ARG(lds >= B, 5, "lds < B");
+  TG_ARG(ldz >= B, 7, "ldz < B");
+  TG_ARG(ldr >= B, 9, "ldr < B");
+  TG_ARG(q, 14, "null q");
+  TG_ARG(ldq >= B, 15, "ldq < B");
+  TG_ARG(e, 16, "null e");
+  TG_ARG(lde >= B, 17, "lde < B");
   hipStream_t st = (hipStream_t)stream;
   tg::Arena ar(ws, ws_bytes);
   float *corr = ar.take<float>(size_t(B) * B);
@@ -735,7 +748,8 @@ static int gptq_quantize_impl(bool loop, void *stream, const float *W, int m, in
   TG_ARG(k >= 1 && k <= n, 6, "rank k must be in [1, n]");
   TG_ARG(ldu >= n, 7, "ldu < n");
   TG_ARG(perm, 8, "null perm");
-  TG_ARG(scale && zero, 9, "null scale/zero");
+  TG_ARG(scale, 9, "null scale");
+  TG_ARG(zero, 10, "null zero");
   const int g = group > 0 ? group : n;
   TG_ARG(n % g == 0, 11, "n % group_size != 0");
   TG_ARG(w_bits >= 2 && w_bits <= 8, 12, "w_bits must be in [2, 8]");
@@ -825,7 +839,7 @@ extern "C" int tg_pack_codes(void *stream, const uint8_t *codes, int m, int n, i
   TG_ARG(codes, 2, "null codes");
   TG_ARG(m > 0, 3, "m <= 0");
   TG_ARG(n > 0, 4, "n <= 0");
-  TG_ARG(w_bits >= 2 && w_bits <= 8, 5, "w_bits must be in [2, 8]");
+  TG_ARG(pack_bits_ok(w_bits), 5, "w_bits must be 2, 3, 4 or 8");
   TG_ARG((int64_t(n) * w_bits) % 32 == 0, 4, "n * w_bits must be a multiple of 32");
   TG_ARG(qweight, 6, "null output");
   const int nw = int((int64_t(n) * w_bits) / 32);
@@ -840,7 +854,7 @@ extern "C" int tg_pack_zeros(void *stream, const float *zero, int m, int G, int 
   TG_ARG(zero, 2, "null zero");
   TG_ARG(m > 0, 3, "m <= 0");
   TG_ARG(G > 0, 4, "G <= 0");
-  TG_ARG(w_bits >= 2 && w_bits <= 8, 5, "w_bits must be in [2, 8]");
+  TG_ARG(pack_bits_ok(w_bits), 5, "w_bits must be 2, 3, 4 or 8");
   TG_ARG((int64_t(m) * w_bits) % 32 == 0, 3, "m * w_bits must be a multiple of 32");
   TG_ARG(qzeros, 7, "null output");
   const int nw = int((int64_t(m) * w_bits) / 32);

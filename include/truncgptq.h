@@ -7,6 +7,18 @@
  * says so.  Scratch memory comes from the caller (`ws`, `ws_bytes`), sized
  * by the matching *_workspace_size() query; the library allocates nothing.
  *
+ * A leading dimension may exceed the width, and a matrix pointer needs only
+ * the alignment of its element type (it may point into the middle of an
+ * allocation): 16-byte loads are taken only where the pointer and the leading
+ * dimension allow them, 8- / 4-byte loads otherwise.  (One exception, by
+ * design: from trailing widths of 6144 up, tg_eigh_values reads pairs of
+ * adjacent columns of A with one 16-byte load that is only 8-byte aligned when
+ * the width or lda is odd; gfx950 global loads permit that.)  Nothing outside the
+ * logical matrix of an output (the columns width .. ld-1 included) is written,
+ * and inputs declared const are left unchanged.  A leading dimension below
+ * the width, a null pointer or a size out of range is rejected with that
+ * argument's index before any device work (tests/test_abi_args.py).
+ *
  * Return value: 0 ok; <0 invalid argument (-(1-based argument index));
  * >0 a hipError_t.  tg_last_error() returns a thread-local message.
  *
@@ -110,7 +122,8 @@ int tg_sketch_accum(void *stream, const void *X, int x_dtype, int64_t T, int n, 
 /* FP64 MFMA GEMM used by every dense stage (exported for tests / reuse):
  * C = alpha op(A) op(B) + beta C, row-major, op(A) M x K, op(B) K x N.
  * Hand-written kernels only (gemm64.hip: 8-wave 128 x 128 tiles for large
- * products, 64 x 64 tiles otherwise); no vendor BLAS is linked. */
+ * products, 64 x 64 tiles otherwise); no vendor BLAS is linked.  lda / ldb are
+ * those of A / B as stored (K x M when transA, N x K when transB). */
 int tg_dgemm(void *stream, int transA, int transB, int M, int N, int K, double alpha,
              const double *A, int lda, const double *B, int ldb, double beta, double *C, int ldc);
 
@@ -144,7 +157,8 @@ int tg_band_tridiag(void *stream, const double *A, int n, int lda, double *d, do
 
 /* ---- A3: truncation rank (gptq_utils.py:97-108) ---------------------------
  * From ascending eigenvalues: S = sqrt(max(L, 1e-12)) descending, then the
- * rank rule.  Writes S_desc (n) and k (int32, device) -- no host sync. */
+ * rank rule.  Writes S_desc (n) and k (int32, device) -- no host sync.
+ * `rule` is a tg_rank_rule; any other value is rejected (-5). */
 int tg_truncation_rank(void *stream, const double *w_asc, int n, double threshold, int rule,
                        double *S_desc, int32_t *k_dev);
 
@@ -233,13 +247,17 @@ int tg_pred_error(void *stream, const float *W, const float *Wq, int m, int n, i
                   size_t ws_bytes);
 
 /* ---- A7: Quantizer.find_params (gptq_utils.py:249-266) --------------------
- * W (m x n f32, ld ldw) -> scale, zero (m x n/g f32, ld n/g); g = group or n. */
+ * W (m x n f32, ld ldw) -> scale, zero (m x n/g f32, ld n/g); g = group, or n
+ * when group <= 0.  Any g >= 1 that divides n is served, g = 1 and groups
+ * narrower than a wave included. */
 int tg_group_params(void *stream, const float *W, int m, int n, int ldw, int group, int w_bits,
                     int sym, float *scale, float *zero);
 
 /* ---- A9: triton_process_block (gptq_utils.py:393-453, kernel :298-386) ----
  * One block: w, s, z (m x B f32, ld ldw/lds/ldz), R (B x B f32, ld ldr).
- * Outputs q (dequantised) and e (raw error), m x B, ld ldq / lde. */
+ * Outputs q (dequantised) and e (raw error), m x B, ld ldq / lde.  Each of the
+ * six leading dimensions must be >= B (rejected with its own index: -3, -5,
+ * -7, -9, -15, -17). */
 size_t tg_process_block_workspace_size(int B);
 int tg_process_block(void *stream, const float *w, int ldw, const float *s, int lds,
                      const float *z, int ldz, const float *R, int ldr, int m, int B, int minq,
@@ -284,7 +302,9 @@ int tg_hinv_chol(void *stream, const double *H, int n, int ldh, const int64_t *p
 /* ---- A13: packing (absent in the reference; README.md:133) ----------------
  * codes (m x n uint8, offset form) -> qweight (n*b/32 x m int32, bit stream
  * along in_features; AutoGPTQ layout for b in {2,3,4,8}); zero (m x G f32)
- * -> qzeros (G x m*b/32 int32, stored zero + 2^(b-1) when sym). */
+ * -> qzeros (G x m*b/32 int32, stored zero + 2^(b-1) when sym).  Any other
+ * w_bits (5, 6, 7 included) is rejected (-5), as tg_dequant_packed and tg_qgemm
+ * reject it: no consumer reads such a stream. */
 int tg_pack_codes(void *stream, const uint8_t *codes, int m, int n, int w_bits, int32_t *qweight);
 int tg_pack_zeros(void *stream, const float *zero, int m, int G, int w_bits, int sym,
                   int32_t *qzeros);
