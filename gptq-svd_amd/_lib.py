@@ -40,6 +40,11 @@ _SIGS = {
     "tg_profile_query": ([_i, ctypes.POINTER(_d), ctypes.POINTER(_i64), ctypes.POINTER(_d),
                           ctypes.POINTER(_d), ctypes.POINTER(_i64)], _i),
     "tg_dgemm": ([_vp, _i, _i, _i, _i, _i, _d, _vp, _i, _vp, _i, _d, _vp, _i], _i),
+    "tg_gemm64_probe_workspace_size": ([_i, _i, _i, _i], _sz),
+    "tg_gemm64_probe": ([_vp, _i, _i, _i, _i, _i, _i, _d, _vp, _i, _vp, _i, _d, _vp, _i, _i, _vp,
+                         _sz], _i),
+    "tg_gemm64_chunked": ([_vp, _i, _i, ctypes.POINTER(_i64), _i, _d, _vp, _i, _vp, _i, _d, _vp,
+                           _i], _i),
     "tg_eigh_workspace_size": ([_i], _sz),
     "tg_eigh_values": ([_vp, _vp, _i, _i, _vp, _vp, _sz], _i),
     "tg_eigh_vectors": ([_vp, _i, _vp, _i, _vp, _i, _vp, _sz], _i),

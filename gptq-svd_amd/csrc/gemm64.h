@@ -8,8 +8,10 @@
 
 namespace tg {
 // C = alpha * op(A) op(B) + beta * C, row-major; op(A) is M x K, op(B) is K x N.
-// C = alpha A B + beta C, A (M x K) upper triangular row-major (zeros below
-// the diagonal are not read); own FP64 MFMA kernel.
+// C = alpha A B + beta C, A (M x K) upper triangular row-major; own FP64 MFMA
+// kernel.  The zeros below the diagonal are skipped per tile row: rows tm ..
+// of a tile sum from k = tm, so the zeros inside the tile-sized diagonal
+// blocks are read (and must be zeros), those strictly below them are not.
 hipError_t dgemm_upper_a(hipStream_t st, int M, int N, int K, double alpha, const double *A,
                          int64_t lda, const double *B, int64_t ldb, double beta, double *C,
                          int64_t ldc);

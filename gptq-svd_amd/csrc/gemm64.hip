@@ -774,3 +774,94 @@ extern "C" int tg_syrk_accum(void *stream, const void *X, int x_dtype, int64_t r
   TG_HIP(e);
   return 0;
 }
+
+// ---------------------------------------------------------------------------
+// Test hooks onto the rest of the family (truncgptq.h: tests / tools only).
+// ---------------------------------------------------------------------------
+extern "C" size_t tg_gemm64_probe_workspace_size(int op, int M, int N, int splits) {
+  if (op != TG_G64_SPLITK || M <= 0 || N <= 0 || splits <= 0) return 0;
+  return tg::dgemm_splitk_scratch(M, N, splits);
+}
+
+extern "C" int tg_gemm64_probe(void *stream, int op, int transA, int transB, int M, int N, int K,
+                               double alpha, const double *A, int lda, const double *B, int ldb,
+                               double beta, double *C, int ldc, int splits, void *ws,
+                               size_t ws_bytes) {
+  hipStream_t st = (hipStream_t)stream;
+  TG_ARG(op >= TG_G64_GEMM && op <= TG_G64_SYRK_NT, 2, "unknown op");
+  TG_ARG(N >= 0, 6, "negative size");
+  TG_ARG(A, 9, "null A");
+  TG_ARG(C, 14, "null C");
+  TG_ARG(ldc >= N, 15, "ldc < N");
+  if (op >= TG_G64_SYRK_TN) {
+    TG_ARG(K >= 0, 7, "negative size");
+    TG_ARG(lda >= (op == TG_G64_SYRK_NT ? K : N), 10, "ldx < columns of X as stored");
+    hipError_t e;
+    switch (op) {
+      case TG_G64_SYRK_TN: e = tg::dsyrk_tn(st, N, K, alpha, A, lda, beta, C, ldc); break;
+      case TG_G64_SYRK_TN_UPPER: e = tg::dsyrk_tn_upper(st, N, alpha, A, lda, beta, C, ldc); break;
+      case TG_G64_SYRK_TN_LOWER: e = tg::dsyrk_tn_lower(st, N, K, alpha, A, lda, beta, C, ldc); break;
+      default: e = tg::dsyrk_nt(st, N, K, alpha, A, lda, beta, C, ldc); break;
+    }
+    TG_HIP(e);
+    return 0;
+  }
+  TG_ARG(M >= 0, 5, "negative size");
+  if (op == TG_G64_SUM_PARTIALS) {
+    TG_ARG(splits >= 1, 16, "nz < 1");
+    TG_HIP(tg::sum_partials(st, A, splits, M, N, alpha, beta, C, ldc));
+    return 0;
+  }
+  TG_ARG(K >= 0, 7, "negative size");
+  TG_ARG(B, 11, "null B");
+  if (op == TG_G64_UPPER_A) {
+    TG_ARG(!transA, 3, "dgemm_upper_a takes no transposes");
+    TG_ARG(!transB, 4, "dgemm_upper_a takes no transposes");
+  }
+  TG_ARG(lda >= (transA ? M : K), 10, "lda < columns of A as stored");
+  TG_ARG(ldb >= (transB ? K : N), 12, "ldb < columns of B as stored");
+  if (op == TG_G64_UPPER_A) {
+    TG_HIP(tg::dgemm_upper_a(st, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc));
+  } else if (op == TG_G64_SPLITK) {
+    TG_ARG(splits >= 1, 16, "splits < 1");
+    const size_t need = tg_gemm64_probe_workspace_size(op, M, N, splits);
+    TG_ARG(ws || need == 0, 17, "null workspace");
+    TG_ARG(ws_bytes >= need, 18, "workspace too small");
+    TG_HIP(tg::dgemm_splitk(st, transA != 0, transB != 0, M, N, K, alpha, A, lda, B, ldb, beta, C,
+                            ldc, splits, (double *)ws));
+  } else {
+    TG_HIP(tg::dgemm(st, transA != 0, transB != 0, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc));
+  }
+  return 0;
+}
+
+extern "C" int tg_gemm64_chunked(void *stream, int transA, int transB, const int64_t *spec,
+                                 int tri, double alpha, const double *A, int lda, const double *B,
+                                 int ldb, double beta, double *C, int ldc) {
+  TG_ARG(spec, 4, "null spec");
+  for (int f : {0, 1, 2, 9, 10, 11})
+    TG_ARG(spec[f] >= INT32_MIN && spec[f] <= INT32_MAX, 4, "spec field out of int range");
+  const tg::ChunkSpec cs{int(spec[0]), int(spec[1]), int(spec[2]), spec[3], spec[4], spec[5],
+                         spec[6],      spec[7],      spec[8],      int(spec[9]), int(spec[10]),
+                         int(spec[11])};
+  TG_ARG(cs.c > 0, 4, "spec: c <= 0");
+  TG_ARG(cs.nc >= 0, 4, "spec: nc < 0");
+  TG_ARG(cs.m >= 0, 4, "spec: m < 0");
+  TG_ARG(cs.nc == 0 || int64_t(cs.m) >= int64_t(cs.nc - 1) * cs.c, 4, "spec: m < (nc - 1) * c");
+  TG_ARG(tri >= 0 && tri <= 2, 5, "tri not 0, 1 or 2");
+  TG_ARG(tri == 0 || !transA, 2, "a triangular operand takes no transposes");
+  TG_ARG(tri == 0 || !transB, 3, "a triangular operand takes no transposes");
+  TG_ARG(A, 7, "null A");
+  TG_ARG(B, 9, "null B");
+  TG_ARG(C, 12, "null C");
+  // the widest chunk (the last one may be longer or shorter than c)
+  const int64_t hmax = cs.nc == 0 ? 0 : std::max<int64_t>(cs.c, cs.m - int64_t(cs.nc - 1) * cs.c);
+  const int64_t M = cs.M < 0 ? hmax : cs.M, N = cs.N < 0 ? hmax : cs.N, K = cs.K < 0 ? hmax : cs.K;
+  TG_ARG(tri == 0 || cs.nc == 0 || (M >= 1 && N >= 1), 4, "spec: empty triangular problem");
+  TG_ARG(lda >= (transA ? M : K), 8, "lda < columns of a chunk of A as stored");
+  TG_ARG(ldb >= (transB ? K : N), 10, "ldb < columns of a chunk of B as stored");
+  TG_ARG(ldc >= N, 13, "ldc < N of a chunk");
+  TG_HIP(tg::dgemm_chunked((hipStream_t)stream, transA != 0, transB != 0, cs, alpha, A, lda, B,
+                           ldb, beta, C, ldc, tri));
+  return 0;
+}

@@ -127,6 +127,58 @@ int tg_sketch_accum(void *stream, const void *X, int x_dtype, int64_t T, int n, 
 int tg_dgemm(void *stream, int transA, int transB, int M, int N, int K, double alpha,
              const double *A, int lda, const double *B, int ldb, double beta, double *C, int ldc);
 
+/* The rest of the internal FP64 GEMM family (gemm64.h), one switch onto the
+ * functions the dense stages call.  Tests / tools only; product code does not
+ * come through here.  Stream-ordered, synchronises nothing.  Row-major, C (ld
+ * ldc) updated in place as C = alpha * (product) + beta * C; with beta == 0, C
+ * is not read.  Per op:
+ *   TG_G64_GEMM          dgemm, the arguments of tg_dgemm;
+ *   TG_G64_UPPER_A       dgemm_upper_a: C = alpha A B + beta C with A (M x K,
+ *                        M <= K) upper triangular; of A's zeros only those in
+ *                        the tile rows' own diagonal blocks are read (the sum
+ *                        of the tile row starting at tm begins at k = tm);
+ *                        transA = transB = 0;
+ *   TG_G64_SPLITK        dgemm_splitk over `splits` K ranges; ws holds
+ *                        tg_gemm64_probe_workspace_size(op, M, N, splits) bytes
+ *                        (M * N * splits doubles, written before they are read);
+ *   TG_G64_SUM_PARTIALS  sum_partials: C (M x N) = alpha sum_z P_z + beta C,
+ *                        A = P (splits = nz >= 1 slices of M x N, ld N);
+ *   TG_G64_SYRK_TN       dsyrk_tn: C (n x n) = alpha X^T X + beta C, X (K x n),
+ *                        lower tiles computed and mirrored: C is exactly
+ *                        symmetric when beta C was;
+ *   TG_G64_SYRK_TN_UPPER dsyrk_tn_upper: the same for an upper-triangular X
+ *                        (n x n, strict lower triangle exactly 0; K ignored);
+ *   TG_G64_SYRK_TN_LOWER dsyrk_tn_lower: the 64 x 64 lower and diagonal tiles
+ *                        only; the strict upper triangle outside the diagonal
+ *                        tiles is not written;
+ *   TG_G64_SYRK_NT       dsyrk_nt: C (n x n) = alpha X X^T + beta C, X (n x K).
+ * For the SYRK ops N is n, A is X and lda is ldx; M, B, ldb, transA and transB
+ * are ignored (B may be NULL).  SUM_PARTIALS ignores lda, B, ldb, K.  Only
+ * SPLITK takes a workspace; every other op needs 0 bytes (ws may be NULL). */
+enum tg_gemm64_op { TG_G64_GEMM = 0, TG_G64_UPPER_A = 1, TG_G64_SPLITK = 2,
+                    TG_G64_SUM_PARTIALS = 3, TG_G64_SYRK_TN = 4, TG_G64_SYRK_TN_UPPER = 5,
+                    TG_G64_SYRK_TN_LOWER = 6, TG_G64_SYRK_NT = 7 };
+size_t tg_gemm64_probe_workspace_size(int op, int M, int N, int splits);
+int tg_gemm64_probe(void *stream, int op, int transA, int transB, int M, int N, int K,
+                    double alpha, const double *A, int lda, const double *B, int ldb,
+                    double beta, double *C, int ldc, int splits, void *ws, size_t ws_bytes);
+/* dgemm_chunked (gemm64.h), the grouped GEMM of the band reduction and the
+ * triangular inverse.  Tests / tools only; synchronises nothing.  spec (host
+ * memory, read during the call) holds the 12 fields of ChunkSpec in order:
+ * c, nc, m, a_kb, a_z, b_kb, b_z, c_kb, c_z, M, N, K.  Chunk z = 0 .. nc-1
+ * covers [kb, ke) of a length-m axis, kb = z c, ke = m for the last chunk and
+ * kb + c otherwise, and computes C_z = alpha op(A_z) op(B_z) + beta C_z with
+ * X_z = X + kb x_kb + z x_z (element offsets) and M / N / K the given value or,
+ * when negative, the chunk length ke - kb.  Needs c > 0, nc >= 0, m >= (nc-1) c
+ * and lda / ldb / ldc at least the widths of one chunk's operands as stored;
+ * keeping the chunks inside the caller's buffers is the caller's business.
+ * tri = 1: every A_z is upper triangular, tri = 2: every B_z (K x N) is; the
+ * zero triangle is skipped per tile, so of its zeros only those in the tiles'
+ * diagonal blocks are read.  tri != 0 takes no transposes and M, N >= 1. */
+int tg_gemm64_chunked(void *stream, int transA, int transB, const int64_t *spec, int tri,
+                      double alpha, const double *A, int lda, const double *B, int ldb,
+                      double beta, double *C, int ldc);
+
 /* ---- A2: symmetric eigensolver (torch.linalg.eigh, gptq_utils.py:93) ----
  * Stage 1: A (n x n symmetric, full storage, destroyed) -> tridiagonal
  * (Householder, lower) + all eigenvalues ascending in w_asc (n).  The

@@ -99,6 +99,58 @@ CASES = {
 }
 CASES["tg_gptq_quantize_loop"] = CASES["tg_gptq_quantize"]
 
+
+class Spec(ctypes.c_int64 * 12):
+    """A ChunkSpec for tg_gemm64_chunked (c, nc, m, six offsets, M, N, K) that
+    prints as its values, so the test ids do not carry an address."""
+
+    def __str__(self):
+        return "spec" + "_".join(str(v) for v in self)
+
+
+def spec(c=4, nc=2, m=8, M=3, N=5, K=6):
+    return Spec(c, nc, m, 0, 0, 0, 0, 0, 0, M, N, K)
+
+
+# the test hooks onto the internal FP64 GEMM family: op 0 / 1 / 2 take A (M x K),
+# B (K x N) like tg_dgemm, op 3 sums nz slices, ops 4..7 are SYRKs of X = A
+CASES.update({
+    "tg_gemm64_probe": ([None, 0, 0, 0, 4, 5, 6, 1.0, P, 6, P, 5, 0.0, P, 5, 1, None, 0],
+                        [(2, -1), (2, 8), (5, -1), (6, -1), (7, -1), (9, None), (10, 5),
+                         (11, None), (12, 4), (14, None), (15, 4)]),
+    "tg_gemm64_probe/tt": ([None, 0, 1, 1, 4, 5, 6, 1.0, P, 4, P, 6, 0.0, P, 5, 1, None, 0],
+                           [(10, 3), (12, 5)]),
+    "tg_gemm64_probe/upper_a": ([None, 1, 0, 0, 4, 5, 6, 1.0, P, 6, P, 5, 0.0, P, 5, 1, None, 0],
+                                [(3, 1), (4, 1), (10, 5), (12, 4), (15, 4)]),
+    "tg_gemm64_probe/splitk": ([None, 2, 0, 0, 4, 5, 6, 1.0, P, 6, P, 5, 0.0, P, 5, 2, P, BIG],
+                               [(10, 5), (12, 4), (15, 4), (16, 0), (17, None),
+                                (18, 4 * 5 * 2 * 8 - 1)]),
+    "tg_gemm64_probe/sum_partials": ([None, 3, 0, 0, 4, 5, 0, 1.0, P, 0, None, 0, 0.0, P, 5, 2,
+                                      None, 0],
+                                     [(5, -1), (6, -1), (9, None), (14, None), (15, 4), (16, 0)]),
+    "tg_gemm64_probe/syrk_tn": ([None, 4, 0, 0, 0, 5, 6, 1.0, P, 5, None, 0, 0.0, P, 5, 0, None, 0],
+                                [(6, -1), (7, -1), (9, None), (10, 4), (14, None), (15, 4)]),
+    "tg_gemm64_probe/syrk_tn_upper": ([None, 5, 0, 0, 0, 5, 0, 1.0, P, 5, None, 0, 0.0, P, 5, 0,
+                                       None, 0], [(10, 4), (15, 4)]),
+    "tg_gemm64_probe/syrk_tn_lower": ([None, 6, 0, 0, 0, 5, 6, 1.0, P, 5, None, 0, 0.0, P, 5, 0,
+                                       None, 0], [(10, 4), (15, 4)]),
+    "tg_gemm64_probe/syrk_nt": ([None, 7, 0, 0, 0, 5, 6, 1.0, P, 6, None, 0, 0.0, P, 5, 0, None, 0],
+                                [(10, 5), (15, 4)]),
+    "tg_gemm64_chunked": ([None, 0, 0, spec(), 0, 1.0, P, 6, P, 5, 0.0, P, 5],
+                          [(4, None), (4, spec(c=0)), (4, spec(nc=-1)), (4, spec(m=-1)),
+                           (4, spec(nc=4)), (4, spec(M=1 << 31)), (5, -1), (5, 3), (7, None),
+                           (8, 5), (9, None), (10, 4), (12, None), (13, 4)]),
+    # M / N / K < 0 stand for the longest chunk: c = 4, nc = 2, m = 11 -> 7
+    "tg_gemm64_chunked/k": ([None, 0, 0, spec(m=11, K=-1), 0, 1.0, P, 7, P, 5, 0.0, P, 5],
+                            [(8, 6)]),
+    "tg_gemm64_chunked/tt": ([None, 1, 1, spec(m=11, M=-1), 0, 1.0, P, 7, P, 6, 0.0, P, 5],
+                             [(8, 6), (10, 5)]),
+    "tg_gemm64_chunked/n": ([None, 0, 0, spec(m=11, N=-1), 0, 1.0, P, 6, P, 7, 0.0, P, 7],
+                            [(10, 6), (13, 6)]),
+    "tg_gemm64_chunked/tri": ([None, 0, 0, spec(), 1, 1.0, P, 6, P, 5, 0.0, P, 5],
+                              [(2, 1), (3, 1), (4, spec(M=0)), (8, 5)]),
+})
+
 PARAMS = [pytest.param(name, idx, bad, id=f"{name}-arg{idx}-{bad}")
           for name, (_, bads) in CASES.items() for idx, bad in bads]
 
