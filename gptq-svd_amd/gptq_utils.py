@@ -416,12 +416,32 @@ def process_hessian(H: torch.Tensor, actorder: bool = False,
 # ---------------------------------------------------------------------------
 class Quantizer:
     """Static-group min/max (asym) or absmax (sym) quantizer; same fields and
-    shapes as the reference (scale/zero: (m, n/g, 1) float32)."""
+    shapes as the reference (scale/zero: (m, n/g, 1) float32).
 
-    def __init__(self, w_bits: int = 4, group_size: int = 128, sym: bool = False):
+    ``clip_search=True`` (A7c, new): each group's range is shrunk by the factor
+    p = 1 - i / clip_grid, i = 0 .. clip_steps, that minimises the
+    round-to-nearest error weighted per column by ``col_weight`` (n values
+    >= 0, e.g. diag(H); None = unweighted), the fused search of
+    tg_group_params_clip.  i = 0 is the plain min/max (absmax) choice, so the
+    weighted error never rises.  ``clip_choice`` (m, n/g int32) and
+    ``clip_objective`` (m, n/g, 2 float64: {J_0, J_chosen}) hold the last
+    search's results."""
+
+    def __init__(self, w_bits: int = 4, group_size: int = 128, sym: bool = False,
+                 clip_search: bool = False, clip_grid: int = 100, clip_steps: int = 80,
+                 col_weight: Optional[torch.Tensor] = None):
         self.w_bits = w_bits
         self.group_size = group_size
         self.sym = sym
+        if not 0 <= clip_steps < clip_grid:
+            raise ValueError(f"Quantizer: need 0 <= clip_steps < clip_grid, got clip_steps="
+                             f"{clip_steps}, clip_grid={clip_grid}")
+        self.clip_search = bool(clip_search)
+        self.clip_grid = int(clip_grid)
+        self.clip_steps = int(clip_steps)
+        self.col_weight = col_weight
+        self.clip_choice = None
+        self.clip_objective = None
         if self.sym:
             half_range = 2 ** (w_bits - 1) - 1
             self.max_q = half_range
@@ -441,9 +461,26 @@ class Quantizer:
         G = n // g
         scale = torch.empty((m, G), dtype=torch.float32, device=W.device)
         zero = torch.empty((m, G), dtype=torch.float32, device=W.device)
-        with torch.cuda.device(W.device):
-            call("tg_group_params", stream(), ptr(W), m, n, n, self.group_size, self.w_bits,
-                 int(self.sym), ptr(scale), ptr(zero))
+        if self.clip_search:
+            h = self.col_weight
+            if h is not None:
+                h = torch.as_tensor(h).detach().to(device=W.device, dtype=torch.float32)
+                h = h.reshape(-1).clamp_min(0.0).contiguous()
+                if h.numel() != n:
+                    raise RuntimeError(f"Quantizer.find_params: col_weight has {h.numel()} "
+                                       f"entries, the weights have {n} columns")
+            choice = torch.empty((m, G), dtype=torch.int32, device=W.device)
+            objective = torch.empty((m, G, 2), dtype=torch.float64, device=W.device)
+            with torch.cuda.device(W.device):
+                call("tg_group_params_clip", stream(), ptr(W), m, n, n, ptr(h), self.group_size,
+                     self.w_bits, int(self.sym), self.clip_grid, self.clip_steps, ptr(scale),
+                     ptr(zero), ptr(choice), ptr(objective))
+            self.clip_choice = choice
+            self.clip_objective = objective
+        else:
+            with torch.cuda.device(W.device):
+                call("tg_group_params", stream(), ptr(W), m, n, n, self.group_size, self.w_bits,
+                     int(self.sym), ptr(scale), ptr(zero))
         self.scale = scale.unsqueeze(-1)
         self.zero = zero.unsqueeze(-1)
 

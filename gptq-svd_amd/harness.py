@@ -288,19 +288,22 @@ def check_factor_agrees(R: torch.Tensor, perm: torch.Tensor, pg=None) -> None:
 
 def quantize_linear_sharded(W: torch.Tensor, R: torch.Tensor, perm: torch.Tensor,
                             w_bits: int, group_size: int, sym: bool, block_size: int,
-                            use_triton: bool, pg=None):
+                            use_triton: bool, pg=None, **quantizer_kw):
     """gptq_fwrd over this rank's rows of W, gathered: returns (dequantised W,
-    rank, Quantizer holding the gathered codes / scale / zero) on every rank."""
+    rank, Quantizer holding the gathered codes / scale / zero) on every rank.
+    `quantizer_kw`: further Quantizer arguments (the clip search's settings and
+    column weights; its per-group results are gathered too)."""
     world, rank = _world(pg)
     m, n = W.shape
     r0, r1 = tgdist.shard_rows(m, world, rank)
-    q = Quantizer(w_bits=w_bits, group_size=group_size, sym=sym)
+    q = Quantizer(w_bits=w_bits, group_size=group_size, sym=sym, **quantizer_kw)
     G = n // (group_size if group_size > 0 else n)
     if r1 > r0:
         Wq, k = gptq_fwrd(W[r0:r1], R, q, perm, block_size=block_size, use_triton=use_triton)
         Wq = Wq.to(W.dtype)
         codes = q.codes.to(torch.uint8)
         scale, zero = q.scale.squeeze(-1).float(), q.zero.squeeze(-1).float()
+        choice, objective = q.clip_choice, q.clip_objective
     else:
         # no rows here (m < world): still join every gather
         k = R.shape[0]
@@ -308,10 +311,15 @@ def quantize_linear_sharded(W: torch.Tensor, R: torch.Tensor, perm: torch.Tensor
         codes = torch.empty((0, n), dtype=torch.uint8, device=W.device)
         scale = torch.empty((0, G), dtype=torch.float32, device=W.device)
         zero = torch.empty((0, G), dtype=torch.float32, device=W.device)
+        choice = torch.empty((0, G), dtype=torch.int32, device=W.device)
+        objective = torch.empty((0, G, 2), dtype=torch.float64, device=W.device)
     Wq = tgdist.all_gather_rows(Wq, m, pg)
     q.codes = tgdist.all_gather_rows(codes, m, pg)
     q.scale = tgdist.all_gather_rows(scale, m, pg).unsqueeze(-1)
     q.zero = tgdist.all_gather_rows(zero, m, pg).unsqueeze(-1)
+    if q.clip_search:
+        q.clip_choice = tgdist.all_gather_rows(choice, m, pg)
+        q.clip_objective = tgdist.all_gather_rows(objective, m, pg)
     return Wq, k, q
 
 
@@ -325,7 +333,8 @@ def quantize_model(model: nn.Module, input_ids_list: Sequence[torch.Tensor], mod
                    clock: Optional[StageClock] = None, save_path: Optional[str] = None,
                    run_config: Optional[Dict[str, Any]] = None,
                    staged: Optional[bool] = None, sketch_ratio: float = 4.0,
-                   sketch_seed: Optional[int] = None) -> Dict[str, Any]:
+                   sketch_seed: Optional[int] = None, clip_search: bool = False,
+                   clip_grid: int = 100, clip_steps: int = 80) -> Dict[str, Any]:
     """Quantise every sequenced linear of `model` in place (layer by layer).
 
     mode "eigh" = TruncGPTQ (process_hessian_alt + gptq_fwrd(use_triton=True));
@@ -339,6 +348,14 @@ def quantize_model(model: nn.Module, input_ids_list: Sequence[torch.Tensor], mod
     None draws each Sketcher's seed from torch's default CPU generator, so
     ``torch.manual_seed`` governs the run as in the reference.  Single-process
     only (sharded sketches are not implemented).
+    `clip_search` (A7c): every module's scale / zero come from the clip search
+    of ``Quantizer`` (`clip_grid`, `clip_steps`) instead of the plain min/max,
+    weighted per input column by diag(H) in modes "eigh" and "gptq" and by the
+    column sums of squares of the scaled sketch in mode "svd" (proportional to
+    diag(X^T X) in expectation; a positive factor does not move the argmin).
+    Each module logs its weighted round-to-nearest error before and after and
+    the number of groups the search moved, and its ``layer_stats`` entry
+    carries them (``clip_j0``, ``clip_j``, ``clip_moved``, ``clip_groups``).
     `offload`: move each layer to `device` for its turn and back to the CPU
     afterwards (the reference's policy, quantize.py:101, :239); by default
     the model stays where it is (a whole 8B/70B model fits in 288 GB).
@@ -368,6 +385,12 @@ def quantize_model(model: nn.Module, input_ids_list: Sequence[torch.Tensor], mod
         raise ValueError(f"mode must be 'eigh', 'gptq' or 'svd', got {mode!r}")
     if mode == "svd" and _world(pg)[0] > 1:
         raise ValueError("mode 'svd' is single-process")
+    if not 0 <= clip_steps < clip_grid:
+        raise ValueError(f"need 0 <= clip_steps < clip_grid, got clip_steps={clip_steps}, "
+                         f"clip_grid={clip_grid}")
+    # passed on only when the search is on, so a run without it is unchanged
+    clip_kw = (dict(clip_search=True, clip_grid=clip_grid, clip_steps=clip_steps)
+               if clip_search else {})
     if save_path is not None:
         res = run_and_record(model, input_ids_list, save_path, run_config, mode=mode,
                              w_bits=w_bits, group_size=group_size, sym=sym, eps=eps,
@@ -375,7 +398,8 @@ def quantize_model(model: nn.Module, input_ids_list: Sequence[torch.Tensor], mod
                              damp_percent=damp_percent, use_adaptive_eps=use_adaptive_eps,
                              batch_size=batch_size, device=device, block_size=block_size,
                              pack=pack, offload=offload, pg=pg, early_stop=early_stop, clock=clock,
-                             staged=staged, sketch_ratio=sketch_ratio, sketch_seed=sketch_seed)
+                             staged=staged, sketch_ratio=sketch_ratio, sketch_seed=sketch_seed,
+                             **clip_kw)
         return res
     t_start = time.time()
     world, rank = _world(pg)
@@ -457,18 +481,23 @@ def quantize_model(model: nn.Module, input_ids_list: Sequence[torch.Tensor], mod
             R_x = None
         if clock:
             clock.stop(f"factor_n{H.shape[1]}", ev)
+        qkw = dict(clip_kw)
+        if clip_search:
+            # the search's column weights, taken before H is freed
+            qkw["col_weight"] = (H.float().square().sum(dim=0) if mode == "svd"
+                                 else torch.diagonal(H).clone())
         del H
         if world > 1:
             check_factor_agrees(R, perm, pg)
         ev = clock.start() if clock else None
         for name in names:
             sub = _submodule(layer, name)
-            q = Quantizer(w_bits=w_bits, group_size=group_size, sym=sym)
+            q = Quantizer(w_bits=w_bits, group_size=group_size, sym=sym, **qkw)
             t0 = time.time()
             if world > 1:
                 W = sub.weight.data.float()
                 Wq, k, q = quantize_linear_sharded(W, R, perm, w_bits, group_size, sym,
-                                                   block_size, mode != "gptq", pg)
+                                                   block_size, mode != "gptq", pg, **qkw)
                 if R_x is not None and rank == 0:
                     log_quantization_error(W, Wq, R_x, perm)
             else:
@@ -482,7 +511,15 @@ def quantize_model(model: nn.Module, input_ids_list: Sequence[torch.Tensor], mod
             dt = time.time() - t0
             used = k if mode != "gptq" else "N/A"
             logging.info(f"   {name: <15} | Rank: {str(used): <4} | Time: {dt:.2f}s")
-            stats.append({"name": full, "rank": used, "time": dt})
+            entry = {"name": full, "rank": used, "time": dt}
+            if clip_search:
+                j0, j1 = q.clip_objective.sum(dim=(0, 1)).tolist()
+                moved = int((q.clip_choice != 0).sum().item())
+                logging.info(f"   [Clip] weighted RTN error {j0:.4e} -> {j1:.4e}, "
+                             f"{moved}/{q.clip_choice.numel()} groups clipped")
+                entry.update(clip_j0=j0, clip_j=j1, clip_moved=moved,
+                             clip_groups=q.clip_choice.numel())
+            stats.append(entry)
         if clock:
             clock.stop("quantize", ev)
 
@@ -631,6 +668,8 @@ def run_and_record(model: nn.Module, input_ids_list: Sequence[torch.Tensor], sav
         # what makes a sketch-mode run reproducible (None: every Sketcher drew its
         # seed from torch's default CPU generator, i.e. torch.manual_seed governs)
         cfg["sketch_seed"] = kw.get("sketch_seed")
+    if kw.get("clip_search"):
+        cfg.update(_clip_settings(kw))
     mid = getattr(getattr(model, "config", None), "_name_or_path", None)
     if mid:
         cfg["model_id"] = mid
@@ -656,6 +695,12 @@ def run_and_record(model: nn.Module, input_ids_list: Sequence[torch.Tensor], sav
     return res
 
 
+def _clip_settings(kw: Dict[str, Any]) -> Dict[str, Any]:
+    """The clip search's settings as the run records keep them."""
+    return {"clip_search": True, "clip_grid": int(kw.get("clip_grid", 100)),
+            "clip_steps": int(kw.get("clip_steps", 80))}
+
+
 def _packed_copy(model: nn.Module, res: Dict[str, Any], save_path: str,
                  kw: Dict[str, Any]) -> nn.Module:
     """Save the run's packed checkpoint under ``<save_path>/packed`` and load
@@ -664,9 +709,12 @@ def _packed_copy(model: nn.Module, res: Dict[str, Any], save_path: str,
     import os
     from .export import load_quantized, save_quantized
     path = os.path.join(save_path, "packed")
+    extra = {"mode": kw.get("mode", "eigh")}
+    if kw.get("clip_search"):
+        extra.update(_clip_settings(kw))
     save_quantized(path, model, res["packed"], int(kw.get("w_bits", 4)),
                    int(kw.get("group_size", -1)), bool(kw.get("sym", False)),
-                   extra_config={"mode": kw.get("mode", "eigh")})
+                   extra_config=extra)
     twin = copy.deepcopy(model)
     if next(twin.parameters()).dtype == torch.float32:
         twin = twin.half()

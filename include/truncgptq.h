@@ -305,6 +305,35 @@ int tg_pred_error(void *stream, const float *W, const float *Wq, int m, int n, i
 int tg_group_params(void *stream, const float *W, int m, int n, int ldw, int group, int w_bits,
                     int sym, float *scale, float *zero);
 
+/* ---- A7c: Hessian-weighted clip search for scale / zero (new; candidate 0
+ * is find_params, gptq_utils.py:249-266) ----------------------------------
+ * W (m x n f32, row stride stride_w >= n), groups of g consecutive original
+ * columns (g = group, or n when group <= 0; any g >= 1 dividing n),
+ * col_weight = h (n f32 >= 0; null = all ones), maxq / minq as in Quantizer,
+ * grid >= 1, 0 <= steps < grid.  Candidates i = 0 .. steps with
+ * p = 1.0f - float(i) / float(grid); every f32 operation below is one
+ * correctly rounded operation in the order written, no contraction, true
+ * division.
+ *   asym (mn, mx the group's min, max):
+ *     lo = mn < 0 ? p * mn : mn;  hi = mx > 0 ? p * mx : mx;
+ *     d = max(hi - lo, 1e-5f);  s = d / maxq;  z = clamp(rintf(-lo / s), 0, maxq)
+ *   sym (a the group's max |w|):  s = max(p * a, 1e-5f) / maxq;  z = 0
+ *   objective over the group's elements c (the tail / RTN rounding rule,
+ *   gptq_utils.py:552-553):
+ *     q = clamp(rintf(w_c / s + z), minq, maxq);  dq = (q - z) * s;  e = w_c - dq
+ *     J_i = sum_c double(h_c) * (double(e) * double(e)), summed in fp64 in an
+ *     order that is the same for every candidate and every call (no atomics).
+ * Chosen: the smallest i with minimal J_i (only a strictly smaller J replaces
+ * the best so far).  Candidate 0 is tg_group_params, so steps = 0 reproduces
+ * it bit for bit, and J_chosen <= J_0 always.
+ * Outputs: scale, zero (m x n/g f32, laid out as tg_group_params writes
+ * them); choice (nullable, m x n/g int32: the chosen i); objective (nullable,
+ * m x n/g x 2 doubles: {J_0, J_chosen}).  No workspace. */
+int tg_group_params_clip(void *stream, const float *W, int m, int n, int64_t stride_w,
+                         const float *col_weight, int group, int w_bits, int sym, int grid,
+                         int steps, float *scale, float *zero, int32_t *choice,
+                         double *objective);
+
 /* ---- A9: triton_process_block (gptq_utils.py:393-453, kernel :298-386) ----
  * One block: w, s, z (m x B f32, ld ldw/lds/ldz), R (B x B f32, ld ldr).
  * Outputs q (dequantised) and e (raw error), m x B, ld ldq / lde.  Each of the
