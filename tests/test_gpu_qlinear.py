@@ -1,8 +1,11 @@
 """GPU: packed inference (A14) -- tg_dequant_packed, tg_qgemm (both regimes),
 QuantLinear and export.load_quantized.
 
-Host references are built here from the oracle's packer / unpacker and
-numpy / torch on the CPU:
+Host references come from the oracle's packer / unpacker and numpy / torch on
+the CPU; the helpers (packed_case, host_dequant, exact_reference, raw_bits,
+ulp, regimes) live in qlinear_ref.py, shared with test_gpu_qlinear_edges.py
+(production dispatch and layout edges) and checked on the CPU in
+test_qlinear_ref.py:
 
 1. dequant: bit-exact against float32(code - zero) * float32(scale) rounded
    once to the output type.
@@ -27,7 +30,6 @@ numpy / torch on the CPU:
    two K slabs and the MFMA adds them in the same order as torch's GEMM.)
 """
 import copy
-import functools
 import json
 import os
 import sys
@@ -37,57 +39,14 @@ import pytest
 import torch
 
 from conftest import golden_names, load_golden
+from qlinear_ref import (BITS, TDT, exact_reference, host_dequant, packed_case, raw_bits,
+                         regimes, ulp)
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
 from eval_corpus import ByteTokenizer, corpus  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-BITS = [2, 3, 4, 8]
-TDT = {"f16": torch.float16, "bf16": torch.bfloat16, "f32": torch.float32}
-
-
-def oracle():
-    from oracle import oracle as o
-    return o
-
-
-def group_index(n, g):
-    return np.arange(n) // (g if g > 0 else n)
-
-
-@functools.lru_cache(maxsize=None)
-def packed_case(m, n, g, b, scale_kind, seed=0):
-    """Random codes / zeros / scales packed by the oracle.  Returns the host
-    arrays (codes, zeros unsigned ints; scale (m, G) float32) and the packed
-    numpy tensors."""
-    rng = np.random.default_rng(1000 * b + m + n + seed)
-    G = n // (g if g > 0 else n)
-    codes = rng.integers(0, 2 ** b, size=(m, n))
-    zero = rng.integers(0, 2 ** b, size=(m, G))
-    if scale_kind == "pow2":
-        scale = (2.0 ** rng.integers(-6, -1, size=(m, G))).astype(np.float32)
-    elif scale_kind == "small":      # W^ ~ O(0.05)
-        scale = (rng.uniform(0.05, 0.1, size=(m, G)) / 2 ** (b - 1)).astype(np.float32)
-    else:
-        scale = rng.uniform(1e-3, 2e-2, size=(m, G)).astype(np.float32)
-    qw, qz, sc = oracle().pack_weights(codes, scale, zero.astype(np.float32), b, False)
-    return codes, zero, scale, qw, qz, sc
-
-
-def host_dequant(codes, zero, scale, g, out):
-    """float32(code - zero) * float32(scale), one rounding to `out`; returned
-    as a CPU torch tensor of that dtype."""
-    gi = group_index(codes.shape[1], g)
-    w32 = (codes - zero[:, gi]).astype(np.float32) * scale.astype(np.float32)[:, gi]
-    assert w32.dtype == np.float32
-    return torch.from_numpy(w32).to(TDT[out])
-
-
-def raw_bits(t):
-    t = t.detach().cpu().contiguous()
-    return t.view(torch.int32 if t.dtype == torch.float32 else torch.int16).numpy()
-
 
 def to_dev(qw, qz, sc, scale_dtype):
     return (torch.from_numpy(qw).to(DEV), torch.from_numpy(qz).to(DEV),
@@ -127,10 +86,6 @@ def run_qgemm(x_view, qw_d, qz_d, sc_d, m, n, g, b, y_view, bias=None):
                L.DTYPES[y_view.dtype], y_view.stride(0), L.ptr(ws), nbytes)
 
 
-def regimes(T):
-    return ["gemv", "mfma"] if T <= 16 else ["mfma"]
-
-
 EXACT = [(T, shape, b, xdt, regime)
          for T in (1, 3, 16, 17, 33, 130)
          for shape in ((96, 256, 128), (64, 96, 32))
@@ -159,25 +114,13 @@ def test_qgemm_layout_exact(T, shape, b, xdt, regime, monkeypatch):
     ybuf = torch.full((T, m + 5), SENT, dtype=torch.float32, device=DEV)
     run_qgemm(xbuf[:, :n], qw_d, qz_d, sc_d, m, n, g, b, ybuf[:, :m])
     # host: integers scaled by 2^6 (scales are 2^-6 .. 2^-2)
-    gi = group_index(n, g)
-    w_int = (codes - zero[:, gi]).astype(np.int64) * np.rint(scale[:, gi] * 64).astype(np.int64)
-    y_int = X.astype(np.int64) @ w_int.T
+    want, y_int, _ = exact_reference(X, codes, zero, scale, g)
     assert np.abs(y_int).max() < 2 ** 24
-    want = (y_int.astype(np.float64) / 64).astype(np.float32)
+    want = want.numpy()
     got = ybuf.cpu().numpy()
     assert np.all(got[:, m:] == SENT), "padding of Y was written"
     assert np.array_equal(got[:, :m], want), \
         f"{np.mean(got[:, :m] != want):.3f} of the entries differ"
-
-
-def ulp(y64, dt):
-    """Spacing of `dt` at |y64| (fp16: 11-bit significand, subnormal spacing
-    2^-24; bf16: 8-bit significand)."""
-    a = np.abs(y64)
-    e = np.floor(np.log2(np.maximum(a, 1e-300)))
-    if dt == "f16":
-        return 2.0 ** (np.maximum(e, -14) - 10)
-    return 2.0 ** (np.maximum(e, -126) - 7)
 
 
 NUM = [(T, 512, b, xdt, regime, bias)
