@@ -9,6 +9,7 @@ from .gptq_utils import (HessianAccumulator, Quantizer, Sketcher, gptq_fwrd,  # 
                          log_quantization_error, next_power_of_2, pack_quantized,
                          process_hessian, process_hessian_alt, process_sketch,
                          triton_process_block, truncated_spectral_factor)
-from .qlinear import QuantLinear, dequantize_packed  # noqa: F401
+from .qlinear import (MXQuantLinear, QuantLinear, dequantize_packed,  # noqa: F401
+                      dequantize_packed_mx)
 
 __version__ = "0.1.0"

@@ -87,6 +87,13 @@ _SIGS = {
     "tg_qgemm_workspace_size": ([_i, _i, _i], _sz),
     "tg_qgemm": ([_vp, _vp, _i, _i, _i64, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _i,
                   _i64, _vp, _sz], _i),
+    "tg_group_params_mx": ([_vp, _vp, _i, _i, _i, _i, _vp, _vp], _i),
+    "tg_gptq_quantize_mx": ([_vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp,
+                             _sz], _i),
+    "tg_pack_e8m0": ([_vp, _vp, _i, _i, _vp], _i),
+    "tg_dequant_mx": ([_vp, _vp, _vp, _i, _i, _i, _vp, _i, _i64], _i),
+    "tg_qgemm_mx": ([_vp, _vp, _i, _i, _i64, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _i64, _vp,
+                     _sz], _i),
 }
 
 EXPORTED = []
@@ -99,6 +106,8 @@ for _name, (_args, _res) in _SIGS.items():
     EXPORTED.append(_name)
 
 TG_F16, TG_BF16, TG_F32, TG_F64 = 0, 1, 2, 3
+TG_FMT_MXFP4 = 1
+WEIGHT_FORMATS = {"mxfp4": TG_FMT_MXFP4}    # tg_weight_format; "int" is the uniform integer grid
 RULES = {"none": 0, "energy": 1, "mean_trimmed": 2}
 DTYPES = {torch.float16: TG_F16, torch.bfloat16: TG_BF16, torch.float32: TG_F32,
           torch.float64: TG_F64}

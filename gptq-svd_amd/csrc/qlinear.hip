@@ -101,11 +101,49 @@ __device__ inline float scale_value(const void *sc, int sc_dt, int64_t i) {
   return load_as_float(sc, sc_dt, i);
 }
 
+// ---- MXFP4 (A15) --------------------------------------------------------------
+// The kernels below take a format parameter: FMT_INT decodes (code - zero) *
+// scale; FMT_MX (b = 4, g = 32: every unit is its own group) decodes an E2M1
+// code against the unit's E8M0 byte, read from the (units x m) byte image with
+// one byte per lane.  The grid is looked up doubled, from an 8-byte table, and
+// multiplied by half the scale: 2 grid[i] * 2^(byte - 128) is the
+// same real number as grid[i] * 2^(byte - 127) and it is rounded once, so the
+// bits are those of the contract's single multiply.
+enum { FMT_INT = 0, FMT_MX = 1 };
+
+// 2^(byte - 128) by integer shift into the exponent field; bytes 0 and 1 give
+// the subnormals 2^-128 and 2^-127
+__device__ inline float mx_half_scale(uint32_t byte) {
+  return __uint_as_float(byte >= 2u ? (byte - 1u) << 23 : 0x00200000u << (byte & 1u));
+}
+
+// Value q (0..7) of a packed word w of eight 4-bit codes (sign in bit 3 of a
+// code).  The table {0, .5, 1, 1.5, 2, 3, 4, 6} doubled is eight bytes; one byte
+// permute looks up the four even (or odd) codes of the word at once, selected
+// by their low three bits, and each byte converts to fp32 on its own.  The sign
+// is bit 4 q + 3 of w, shifted to bit 31 and merged under the magnitude.  With
+// q a compile-time constant the selector and the permute are shared by the
+// word's values.
+__device__ inline float mx_value(uint32_t w, int q, float hs) {
+  const uint32_t sel = ((q & 1) ? w >> 4 : w) & 0x07070707u;
+  const uint32_t g2 = __builtin_amdgcn_perm(0x0c080604u, 0x03020100u, sel);
+  const float p = float((g2 >> (8 * (q >> 1))) & 0xffu) * hs;
+  const uint32_t sign = w << (28 - 4 * q);
+  return __uint_as_float((__float_as_uint(p) & 0x7fffffffu) | (sign & 0x80000000u));
+}
+
+// weight i of a unit: s is the scale (FMT_INT) or half the MX scale (FMT_MX)
+template <int B, int FMT>
+__device__ inline float unit_weight(const uint32_t (&w)[B], int i, int z, float s) {
+  if constexpr (FMT == FMT_MX) return mx_value(w[i >> 3], i & 7, s);  // B == 4: 8 codes a word
+  else return float(unit_value<B>(w, i) - z) * s;
+}
+
 // ---------------------------------------------------------------------------
 // tg_dequant_packed: lane = output feature, blockIdx.y = unit of 32 values.
 // General n (the last unit may be short) and any group dividing n.
 // ---------------------------------------------------------------------------
-template <int B>
+template <int B, int FMT = FMT_INT>
 __global__ __launch_bounds__(256) void dequant_kernel(const uint32_t *__restrict__ qw,
                                                       const uint32_t *__restrict__ qz,
                                                       const void *__restrict__ sc, int sc_dt,
@@ -130,10 +168,14 @@ __global__ __launch_bounds__(256) void dequant_kernel(const uint32_t *__restrict
       const int gi = k / g;
       if (gi != cur) {
         cur = gi;
-        z = zero_value(qz + int64_t(gi) * nzw, r, B);
-        s = scale_value(sc, sc_dt, int64_t(gi) * m + r);
+        if constexpr (FMT == FMT_MX) {
+          s = mx_half_scale(static_cast<const uint8_t *>(sc)[int64_t(gi) * m + r]);
+        } else {
+          z = zero_value(qz + int64_t(gi) * nzw, r, B);
+          s = scale_value(sc, sc_dt, int64_t(gi) * m + r);
+        }
       }
-      store_from_float(out, out_dt, int64_t(r) * ldo + k, float(unit_value<B>(w, i) - z) * s);
+      store_from_float(out, out_dt, int64_t(r) * ldo + k, unit_weight<B, FMT>(w, i, z, s));
     }
   }
 }
@@ -161,7 +203,7 @@ int gemv_units_per_wg(int m, int n) {
 
 // (waves per SIMD bounded from below: without it the scheduler hoists every
 // LDS read of a unit and takes all 256 registers)
-template <int B, int DT, int TT>
+template <int B, int DT, int TT, int FMT = FMT_INT>
 __global__ __launch_bounds__(256, TT >= 16 ? 2 : 4) void qgemv_kernel(const uint16_t *__restrict__ X, int T,
                                                     int64_t ldx, const uint32_t *__restrict__ qw,
                                                     const uint32_t *__restrict__ qz,
@@ -194,11 +236,15 @@ __global__ __launch_bounds__(256, TT >= 16 ? 2 : 4) void qgemv_kernel(const uint
     uint32_t w[B];
 #pragma unroll
     for (int j = 0; j < B; ++j) w[j] = qw[(int64_t(u) * B + j) * m + rc];
-    const int gi = (u * 32) / g;  // g % 32 == 0: a unit lies in one group
-    if (gi != cur) {
-      cur = gi;
-      z = zero_value(qz + int64_t(gi) * nzw, rc, B);
-      s = scale_value(sc, sc_dt, int64_t(gi) * m + rc);
+    if constexpr (FMT == FMT_MX) {  // a unit is a group: its byte, one per lane
+      s = mx_half_scale(static_cast<const uint8_t *>(sc)[int64_t(u) * m + rc]);
+    } else {
+      const int gi = (u * 32) / g;  // g % 32 == 0: a unit lies in one group
+      if (gi != cur) {
+        cur = gi;
+        z = zero_value(qz + int64_t(gi) * nzw, rc, B);
+        s = scale_value(sc, sc_dt, int64_t(gi) * m + rc);
+      }
     }
     const int kl = (u - u0) * 32;
 #pragma unroll
@@ -206,7 +252,7 @@ __global__ __launch_bounds__(256, TT >= 16 ? 2 : 4) void qgemv_kernel(const uint
       float wv[4];
 #pragma unroll
       for (int c = 0; c < 4; ++c)
-        wv[c] = from_bits<DT>(to_bits<DT>(float(unit_value<B>(w, i4 * 4 + c) - z) * s));
+        wv[c] = from_bits<DT>(to_bits<DT>(unit_weight<B, FMT>(w, i4 * 4 + c, z, s)));
 #pragma unroll
       for (int t = 0; t < TT; ++t) {
         const float4 x = *reinterpret_cast<const float4 *>(&xs[t][kl + i4 * 4]);
@@ -271,7 +317,7 @@ __device__ inline f32x4 mfma16(const uint16_t *a, const uint16_t *b, f32x4 c) {
 // part[z][T][m] and qgemv_reduce_kernel finishes.  The packed words, zero /
 // scale and X of slab k+1 are fetched into registers before the MFMAs of slab
 // k, so their latency hides behind the matrix work.
-template <int B, int DT, int BM>
+template <int B, int DT, int BM, int FMT = FMT_INT>
 __global__ __launch_bounds__(256) void qgemm_mfma_kernel(
     const uint16_t *__restrict__ X, int T, int64_t ldx, int xvec,
     const uint32_t *__restrict__ qw, const uint32_t *__restrict__ qz, const void *__restrict__ sc,
@@ -306,11 +352,15 @@ __global__ __launch_bounds__(256) void qgemm_mfma_kernel(
     if (wvalid) {
 #pragma unroll
       for (int j = 0; j < B; ++j) w[j] = qw[(int64_t(u) * B + j) * m + r];
-      const int gi = (u * 32) / g;  // g % 32 == 0: a unit lies in one group
-      if (gi != cur) {
-        cur = gi;
-        z = zero_value(qz + int64_t(gi) * nzw, r, B);
-        s = scale_value(sc, sc_dt, int64_t(gi) * m + r);
+      if constexpr (FMT == FMT_MX) {
+        s = mx_half_scale(static_cast<const uint8_t *>(sc)[int64_t(u) * m + r]);
+      } else {
+        const int gi = (u * 32) / g;  // g % 32 == 0: a unit lies in one group
+        if (gi != cur) {
+          cur = gi;
+          z = zero_value(qz + int64_t(gi) * nzw, r, B);
+          s = scale_value(sc, sc_dt, int64_t(gi) * m + r);
+        }
       }
     } else {
 #pragma unroll
@@ -343,8 +393,8 @@ __global__ __launch_bounds__(256) void qgemm_mfma_kernel(
       uint32_t pk[16];
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
-        const uint32_t lo = to_bits<DT>(float(unit_value<B>(w, 2 * i) - z) * s);
-        const uint32_t hi = to_bits<DT>(float(unit_value<B>(w, 2 * i + 1) - z) * s);
+        const uint32_t lo = to_bits<DT>(unit_weight<B, FMT>(w, 2 * i, z, s));
+        const uint32_t hi = to_bits<DT>(unit_weight<B, FMT>(w, 2 * i + 1, z, s));
         pk[i] = wvalid ? (lo | (hi << 16)) : 0u;
       }
       u32x4 *dst = reinterpret_cast<u32x4 *>(&Ws[lane][wave * 32]);
@@ -412,12 +462,12 @@ int mfma_slabs_per_split(int T, int m, int n) {
 }
 
 // ---- host dispatch ----------------------------------------------------------
-template <int B, int DT>
+template <int B, int DT, int FMT>
 void launch_gemv(hipStream_t st, int TT, dim3 grid, const uint16_t *X, int T, int64_t ldx,
                  const uint32_t *qw, const uint32_t *qz, const void *sc, int sc_dt, int m, int n,
                  int g, int ub, float *part) {
 #define TG_GV(tt)                                                                              \
-  hipLaunchKernelGGL((qgemv_kernel<B, DT, tt>), grid, dim3(256), 0, st, X, T, ldx, qw, qz, sc, \
+  hipLaunchKernelGGL((qgemv_kernel<B, DT, tt, FMT>), grid, dim3(256), 0, st, X, T, ldx, qw, qz, sc, \
                      sc_dt, m, n, g, ub, part)
   switch (TT) {
     case 1: TG_GV(1); break;
@@ -429,21 +479,21 @@ void launch_gemv(hipStream_t st, int TT, dim3 grid, const uint16_t *X, int T, in
 #undef TG_GV
 }
 
-template <int B>
+template <int B, int FMT = FMT_INT>
 void launch_gemv_b(hipStream_t st, int dt, int TT, dim3 grid, const uint16_t *X, int T,
                    int64_t ldx, const uint32_t *qw, const uint32_t *qz, const void *sc, int sc_dt,
                    int m, int n, int g, int ub, float *part) {
-  if (dt == TG_F16) launch_gemv<B, TG_F16>(st, TT, grid, X, T, ldx, qw, qz, sc, sc_dt, m, n, g, ub, part);
-  else launch_gemv<B, TG_BF16>(st, TT, grid, X, T, ldx, qw, qz, sc, sc_dt, m, n, g, ub, part);
+  if (dt == TG_F16) launch_gemv<B, TG_F16, FMT>(st, TT, grid, X, T, ldx, qw, qz, sc, sc_dt, m, n, g, ub, part);
+  else launch_gemv<B, TG_BF16, FMT>(st, TT, grid, X, T, ldx, qw, qz, sc, sc_dt, m, n, g, ub, part);
 }
 
-template <int B>
+template <int B, int FMT = FMT_INT>
 void launch_mfma_b(hipStream_t st, int dt, dim3 grid, const uint16_t *X, int T, int64_t ldx,
                    int xvec, const uint32_t *qw, const uint32_t *qz, const void *sc, int sc_dt,
                    int m, int n, int g, int sps, float *part, const void *bias, int bias_dt,
                    void *Y, int y_dt, int64_t ldy) {
 #define TG_MFK(DT_, BM_)                                                                       \
-  hipLaunchKernelGGL((qgemm_mfma_kernel<B, DT_, BM_>), grid, dim3(256), 0, st, X, T, ldx, xvec, \
+  hipLaunchKernelGGL((qgemm_mfma_kernel<B, DT_, BM_, FMT>), grid, dim3(256), 0, st, X, T, ldx, xvec, \
                      qw, qz, sc, sc_dt, m, n, g, sps, part, bias, bias_dt, Y, y_dt, ldy)
   const bool big = mfma_rows(T) == 128;
   if (dt == TG_F16) {
@@ -521,6 +571,13 @@ extern "C" size_t tg_qgemm_workspace_size(int T, int m, int n) {
   return size_t(S) * size_t(T) * size_t(m) * sizeof(float) + 256;
 }
 
+struct QgemmIdx { int T, n, ws; };
+static int qgemm_run(const QgemmIdx &ix, int fmt, void *stream, const void *X, int x_dtype, int T,
+                     int64_t ldx, const int32_t *qweight, const int32_t *qzeros,
+                     const void *scales, int scale_dtype, int m, int n, int g, int w_bits,
+                     const void *bias, int bias_dtype, void *Y, int y_dtype, int64_t ldy, void *ws,
+                     size_t ws_bytes);
+
 extern "C" int tg_qgemm(void *stream, const void *X, int x_dtype, int T, int64_t ldx,
                         const int32_t *qweight, const int32_t *qzeros, const void *scales,
                         int scale_dtype, int m, int n, int group, int w_bits, const void *bias,
@@ -545,8 +602,20 @@ extern "C" int tg_qgemm(void *stream, const void *X, int x_dtype, int T, int64_t
   TG_ARG(Y, 16, "null Y");
   TG_ARG(y_dtype == x_dtype || y_dtype == TG_F32, 17, "y_dtype must be x_dtype or TG_F32");
   TG_ARG(ldy >= m, 18, "ldy < m");
+  return qgemm_run(QgemmIdx{4, 11, 19}, FMT_INT, stream, X, x_dtype, T, ldx, qweight, qzeros, scales,
+                   scale_dtype, m, n, g, w_bits, bias, bias_dtype, Y, y_dtype, ldy, ws, ws_bytes);
+}
+
+// The dispatch behind tg_qgemm (FMT_INT) and tg_qgemm_mx (FMT_MX: w_bits = 4,
+// g = 32, scales = the E8M0 byte image, qzeros unused); arguments checked, ix
+// holds the caller's argument indices for the checks that depend on the regime.
+static int qgemm_run(const QgemmIdx &ix, int fmt, void *stream, const void *X, int x_dtype, int T,
+                     int64_t ldx, const int32_t *qweight, const int32_t *qzeros,
+                     const void *scales, int scale_dtype, int m, int n, int g, int w_bits,
+                     const void *bias, int bias_dtype, void *Y, int y_dtype, int64_t ldy, void *ws,
+                     size_t ws_bytes) {
   const int mode = qgemm_mode();
-  TG_ARG(!(mode == 1 && T > GV_MAX_T), 4, "TG_QGEMM=gemv takes T <= 16");
+  TG_ARG(!(mode == 1 && T > GV_MAX_T), ix.T, "TG_QGEMM=gemv takes T <= 16");
   const bool gemv = mode == 1 || (mode == 0 && T <= GV_AUTO_T);
   hipStream_t st = (hipStream_t)stream;
   const uint16_t *Xp = static_cast<const uint16_t *>(X);
@@ -556,15 +625,17 @@ extern "C" int tg_qgemm(void *stream, const void *X, int x_dtype, int T, int64_t
   if (gemv) {
     const int ub = gemv_units_per_wg(m, n);
     const int S = tg::cdiv(n / 32, ub);
-    TG_ARG(ws, 19, "null workspace");
+    TG_ARG(ws, ix.ws, "null workspace");
     tg::Arena arena(ws, ws_bytes);
     float *part = arena.take_aligned<float>(size_t(S) * T * m, 256);
     TG_WS(arena);
     int TT = 1;
     while (TT < T) TT *= 2;
     const dim3 grid(tg::cdiv(m, GV_FEAT), S);
-    TG_ARG(S <= 65535, 11, "n too large");
-    switch (w_bits) {
+    TG_ARG(S <= 65535, ix.n, "n too large");
+    if (fmt == FMT_MX)
+      launch_gemv_b<4, FMT_MX>(st, x_dtype, TT, grid, Xp, T, ldx, qw, qz, scales, scale_dtype, m, n, g, ub, part);
+    else switch (w_bits) {
       case 2: launch_gemv_b<2>(st, x_dtype, TT, grid, Xp, T, ldx, qw, qz, scales, scale_dtype, m, n, g, ub, part); break;
       case 3: launch_gemv_b<3>(st, x_dtype, TT, grid, Xp, T, ldx, qw, qz, scales, scale_dtype, m, n, g, ub, part); break;
       case 4: launch_gemv_b<4>(st, x_dtype, TT, grid, Xp, T, ldx, qw, qz, scales, scale_dtype, m, n, g, ub, part); break;
@@ -577,12 +648,12 @@ extern "C" int tg_qgemm(void *stream, const void *X, int x_dtype, int T, int64_t
     return 0;
   }
 
-  TG_ARG(tg::cdiv(T, mfma_rows(T)) <= 65535, 4, "T too large");
+  TG_ARG(tg::cdiv(T, mfma_rows(T)) <= 65535, ix.T, "T too large");
   const int sps = mfma_slabs_per_split(T, m, n);
   const int S = tg::cdiv(tg::cdiv(n, MF_KS), sps);
   float *part = nullptr;
   if (S > 1) {
-    TG_ARG(ws, 19, "null workspace");
+    TG_ARG(ws, ix.ws, "null workspace");
     tg::Arena arena(ws, ws_bytes);
     part = arena.take_aligned<float>(size_t(S) * T * m, 256);
     TG_WS(arena);
@@ -592,7 +663,10 @@ extern "C" int tg_qgemm(void *stream, const void *X, int x_dtype, int T, int64_t
 #define TG_MF(b)                                                                               \
   launch_mfma_b<b>(st, x_dtype, grid, Xp, T, ldx, xvec, qw, qz, scales, scale_dtype, m, n, g, sps, \
                    part, bias, bias_dtype, Y, y_dtype, ldy)
-  switch (w_bits) {
+  if (fmt == FMT_MX)
+    launch_mfma_b<4, FMT_MX>(st, x_dtype, grid, Xp, T, ldx, xvec, qw, qz, scales, scale_dtype, m, n, g,
+                             sps, part, bias, bias_dtype, Y, y_dtype, ldy);
+  else switch (w_bits) {
     case 2: TG_MF(2); break;
     case 3: TG_MF(3); break;
     case 4: TG_MF(4); break;
@@ -606,4 +680,51 @@ extern "C" int tg_qgemm(void *stream, const void *X, int x_dtype, int T, int64_t
     TG_LAUNCHED();
   }
   return 0;
+}
+
+// ---------------------------------------------------------------------------
+// A15: MXFP4
+// ---------------------------------------------------------------------------
+extern "C" int tg_dequant_mx(void *stream, const int32_t *qweight, const uint8_t *scales_e8m0,
+                             int fmt, int m, int n, void *out, int out_dtype, int64_t ldo) {
+  TG_ARG(qweight, 2, "null qweight");
+  TG_ARG(scales_e8m0, 3, "null scales");
+  TG_ARG(fmt == TG_FMT_MXFP4, 4, "fmt must be TG_FMT_MXFP4");
+  TG_ARG(m > 0, 5, "m <= 0");
+  TG_ARG((int64_t(m) * 4) % 32 == 0, 5, "m * 4 must be a multiple of 32");
+  TG_ARG(n > 0 && n % 32 == 0, 6, "n must be a positive multiple of 32");
+  TG_ARG(out, 7, "null output");
+  TG_ARG(out_dtype == TG_F16 || out_dtype == TG_BF16 || out_dtype == TG_F32, 8,
+         "out_dtype must be TG_F16, TG_BF16 or TG_F32");
+  TG_ARG(ldo >= n, 9, "ldo < n");
+  const int units = n / 32;
+  TG_ARG(units <= 65535, 6, "n too large");
+  hipLaunchKernelGGL((dequant_kernel<4, FMT_MX>), dim3(tg::cdiv(m, 256), units), dim3(256), 0,
+                     (hipStream_t)stream, reinterpret_cast<const uint32_t *>(qweight),
+                     (const uint32_t *)nullptr, scales_e8m0, 0, m, n, 32, out, out_dtype, ldo);
+  TG_LAUNCHED();
+  return 0;
+}
+
+extern "C" int tg_qgemm_mx(void *stream, const void *X, int x_dtype, int T, int64_t ldx,
+                           const int32_t *qweight, const uint8_t *scales_e8m0, int fmt, int m,
+                           int n, const void *bias, int bias_dtype, void *Y, int y_dtype,
+                           int64_t ldy, void *ws, size_t ws_bytes) {
+  TG_ARG(X, 2, "null X");
+  TG_ARG(x_dtype == TG_F16 || x_dtype == TG_BF16, 3, "x_dtype must be TG_F16 or TG_BF16");
+  TG_ARG(T > 0, 4, "T <= 0");
+  TG_ARG(qweight, 6, "null qweight");
+  TG_ARG(scales_e8m0, 7, "null scales");
+  TG_ARG(fmt == TG_FMT_MXFP4, 8, "fmt must be TG_FMT_MXFP4");
+  TG_ARG(m > 0, 9, "m <= 0");
+  TG_ARG(n > 0 && n % 32 == 0, 10, "n must be a positive multiple of 32");
+  TG_ARG(ldx >= n, 5, "ldx < n");
+  TG_ARG((int64_t(m) * 4) % 32 == 0, 9, "m * 4 must be a multiple of 32");
+  TG_ARG(!bias || bias_dtype == TG_F16 || bias_dtype == TG_BF16 || bias_dtype == TG_F32, 12,
+         "bias_dtype must be TG_F16, TG_BF16 or TG_F32");
+  TG_ARG(Y, 13, "null Y");
+  TG_ARG(y_dtype == x_dtype || y_dtype == TG_F32, 14, "y_dtype must be x_dtype or TG_F32");
+  TG_ARG(ldy >= m, 15, "ldy < m");
+  return qgemm_run(QgemmIdx{4, 10, 16}, FMT_MX, stream, X, x_dtype, T, ldx, qweight, nullptr,
+                   scales_e8m0, 0, m, n, 32, 4, bias, bias_dtype, Y, y_dtype, ldy, ws, ws_bytes);
 }

@@ -73,6 +73,69 @@ __global__ __launch_bounds__(256) void group_params_kernel(const float *__restri
 }
 
 // ---------------------------------------------------------------------------
+// A15: MXFP4 (OCP Microscaling: E2M1 elements, one E8M0 scale per 32 values).
+// The contract is stated at tg_group_params_mx / tg_gptq_quantize_mx in
+// include/truncgptq.h.
+// ---------------------------------------------------------------------------
+enum { GRID_INT = 0, GRID_E2M1 = 1 };
+constexpr int MXG = 32;  // values per MX group
+
+// Round x onto the E2M1 grid {0, .5, 1, 1.5, 2, 3, 4, 6} * s, s = 2^E and
+// rs = 2^-E (exact, so x * rs is the bits of x / s): nearest, ties to the even
+// code, saturating at 6.  Branch-free: seven compares, selects and one multiply.
+// Returns qv (+0 for code 0) and the 4-bit code (sign in bit 3; never 8).
+__device__ inline float e2m1_round(float x, float s, float rs, int &code) {
+  const float t = x * rs;
+  const float a = fabsf(t);
+  const int idx = int(a > 0.25f) + int(a >= 0.75f) + int(a > 1.25f) + int(a >= 1.75f) +
+                  int(a > 2.5f) + int(a >= 3.5f) + int(a > 5.0f);
+  // grid[idx]: 0 and 0.5 are idx / 2; from 1.0 up it is (1 + (idx & 1) / 2) 2^((idx >> 1) - 1),
+  // i.e. idx shifted into the exponent / top mantissa bit on top of the bits of 0.5
+  const float gv =
+      idx < 2 ? 0.5f * float(idx) : __uint_as_float(0x3f000000u + (uint32_t(idx) << 22));
+  const float q = gv * s;
+  const bool neg = t < -0.25f;  // t < 0 and idx != 0
+  code = idx | (neg ? 8 : 0);
+  return neg ? -q : q;
+}
+
+// reciprocal of a normal power of two 2^E, |E| <= 126, from its bits
+__device__ inline float pow2_recip(float s) { return __uint_as_float(0x7f000000u - __float_as_uint(s)); }
+
+// One pass, 32 lanes per group (two groups per wave): a = max |w|, the stored
+// byte is max(biased exponent of a - 2, 1), i.e. E = max(floor(log2 a) - 2,
+// -126); zero and subnormal a (exponent field 0) land on E = -126.
+__global__ __launch_bounds__(256) void mx_group_params_kernel(const float *__restrict__ W, int ldw,
+                                                              int G, int64_t groups,
+                                                              float *__restrict__ scale,
+                                                              uint8_t *__restrict__ e8m0) {
+  const int64_t gidx = (int64_t(blockIdx.x) * blockDim.x + threadIdx.x) >> 5;
+  const int l = threadIdx.x & 31;
+  // whole 32-lane groups leave together (groups is a count of lane groups)
+  if (gidx >= groups) return;
+  const int64_t r = gidx / G;
+  const int gi = int(gidx - r * G);
+  float a = fabsf(W[r * ldw + int64_t(gi) * MXG + l]);
+#pragma unroll
+  for (int off = 16; off > 0; off >>= 1) a = fmaxf(a, __shfl_xor(a, off));
+  if (l == 0) {
+    const int ef = int(__float_as_uint(a) >> 23);
+    const int byte = ef - 2 > 1 ? ef - 2 : 1;
+    scale[gidx] = __uint_as_float(uint32_t(byte) << 23);
+    e8m0[gidx] = uint8_t(byte);
+  }
+}
+
+// (m x G) bytes -> (G x m): the image the packed consumers read coalesced
+__global__ void pack_e8m0_kernel(const uint8_t *__restrict__ in, int m, int G,
+                                 uint8_t *__restrict__ out) {
+  const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= int64_t(m) * G) return;
+  const int64_t gi = i / m, r = i - gi * m;
+  out[i] = in[r * G + gi];
+}
+
+// ---------------------------------------------------------------------------
 // Permutation helpers (gptq_utils.py:493, :556-557).
 // ---------------------------------------------------------------------------
 __global__ void invperm_kernel(const int64_t *__restrict__ perm, int n, int32_t *__restrict__ inv,
@@ -162,24 +225,26 @@ struct BlockArgs {
   int dbl;  // two diagonal corr buffers (block_smem(bw, true)): the grid has <= 1 workgroup per CU
 };
 
-template <bool GATHER>
+// GRID_E2M1: z carries the reciprocal scale 2^-E instead of a zero point
+template <bool GATHER, int GRID = GRID_INT>
 __device__ inline void load_sz(const BlockArgs &a, int row, int c, float &s, float &z) {
   if (row >= a.m) {
     s = 1.0f;
-    z = 0.0f;
+    z = GRID == GRID_E2M1 ? 1.0f : 0.0f;
     return;
   }
   if (GATHER) {
     const int gi = a.perm[a.col0 + c] / a.g;
     s = a.scale[size_t(row) * a.G + gi];
-    z = a.zero[size_t(row) * a.G + gi];
+    if constexpr (GRID == GRID_E2M1) z = pow2_recip(s);
+    else z = a.zero[size_t(row) * a.G + gi];
   } else {
     s = a.s[size_t(row) * a.lds + c];
     z = a.z[size_t(row) * a.ldz + c];
   }
 }
 
-template <bool GATHER, bool LOOP>
+template <bool GATHER, bool LOOP, int GRID = GRID_INT>
 __global__ __launch_bounds__(256) void block_kernel(BlockArgs a) {
   extern __shared__ float smem[];
   const int bwp = a.bw + 1;             // odd row stride: lane-per-row access is conflict-free
@@ -225,8 +290,8 @@ __global__ __launch_bounds__(256) void block_kernel(BlockArgs a) {
     const int rr = tid, row = r0 + rr, pw = min(P, a.bw - p0);
 #pragma unroll
     for (int t = 0; t < P; ++t) {
-      if (t < pw) load_sz<GATHER>(a, row, p0 + t, sv[t], zv[t]);
-      else { sv[t] = 1.0f; zv[t] = 0.0f; }
+      if (t < pw) load_sz<GATHER, GRID>(a, row, p0 + t, sv[t], zv[t]);
+      else { sv[t] = 1.0f; zv[t] = GRID == GRID_E2M1 ? 1.0f : 0.0f; }
     }
   };
   float sv[P], zv[P];
@@ -263,24 +328,33 @@ __global__ __launch_bounds__(256) void block_kernel(BlockArgs a) {
       for (int cc = 0; cc < P; ++cc) {
         if (cc < pw) {
           const float x = wv[cc];
-          float t = x / sv[cc];                               // :354
-          t = t + zv[cc];
-          float qi, err, qv;
-          if (LOOP) {                                         // :524-529
-            qi = clampf(rintf(t), a.minq, a.maxq);             // torch.round: half-to-even
-            qv = (qi - zv[cc]) * sv[cc];
-            err = (x - qv) / a.dg[p0 + cc];
+          float err, qv;
+          int code;
+          if constexpr (GRID == GRID_E2M1) {
+            qv = e2m1_round(x, sv[cc], zv[cc], code);
+            err = x - qv;
+            if (LOOP) err = err / a.dg[p0 + cc];
           } else {
-            t = t + 0.5f;
-            qi = clampf(floorf(t), a.minq, a.maxq);            // :355
-            qv = (qi - zv[cc]) * sv[cc];                       // :356
-            err = x - qv;                                      // :358
+            float t = x / sv[cc];                               // :354
+            t = t + zv[cc];
+            float qi;
+            if (LOOP) {                                         // :524-529
+              qi = clampf(rintf(t), a.minq, a.maxq);             // torch.round: half-to-even
+              qv = (qi - zv[cc]) * sv[cc];
+              err = (x - qv) / a.dg[p0 + cc];
+            } else {
+              t = t + 0.5f;
+              qi = clampf(floorf(t), a.minq, a.maxq);            // :355
+              qv = (qi - zv[cc]) * sv[cc];                       // :356
+              err = x - qv;                                      // :358
+            }
+            code = int(qi) + a.code_off;
           }
           if (row < a.m) {
             const int c = p0 + cc;
             a.Q[size_t(row) * a.ldq + c] = qv;
             a.E[size_t(row) * a.lde + c] = err;
-            if (a.codes) a.codes[size_t(row) * a.ldc + c] = uint8_t(int(qi) + a.code_off);
+            if (a.codes) a.codes[size_t(row) * a.ldc + c] = uint8_t(code);
           }
           elc[rr * (P + 1) + cc] = err;
 #pragma unroll
@@ -547,6 +621,7 @@ __global__ __launch_bounds__(256) void cross_gemm_scalar_kernel(const float *__r
 // ---------------------------------------------------------------------------
 // Tail RTN for truncated columns (:547-553) fused with the unpermute (:556-557).
 // ---------------------------------------------------------------------------
+template <int GRID>
 __global__ void finalize_kernel(const float *__restrict__ Wp, const float *__restrict__ Qp,
                                 const uint8_t *__restrict__ cp, const int32_t *__restrict__ inv,
                                 const int32_t *__restrict__ perm, const float *__restrict__ scale,
@@ -561,12 +636,17 @@ __global__ void finalize_kernel(const float *__restrict__ Wp, const float *__res
     int code;
     if (c >= k) {
       const int gi = j / g;  // perm[c] == j
-      const float s = scale[size_t(r) * G + gi], z = zero[size_t(r) * G + gi];
-      float t = Wp[o] / s;
-      t = t + z;
-      const float qi = clampf(rintf(t), minq, maxq);  // torch.round: half-to-even
-      qv = (qi - z) * s;
-      code = int(qi) + code_off;
+      const float s = scale[size_t(r) * G + gi];
+      if constexpr (GRID == GRID_E2M1) {
+        qv = e2m1_round(Wp[o], s, pow2_recip(s), code);
+      } else {
+        const float z = zero[size_t(r) * G + gi];
+        float t = Wp[o] / s;
+        t = t + z;
+        const float qi = clampf(rintf(t), minq, maxq);  // torch.round: half-to-even
+        qv = (qi - z) * s;
+        code = int(qi) + code_off;
+      }
     } else {
       qv = Qp[o];
       code = cp[o];
@@ -631,7 +711,9 @@ hipError_t ensure_block_smem() {
   hipError_t e = hipSuccess;
   for (const void *f : {(const void *)block_kernel<true, false>,
                         (const void *)block_kernel<false, false>,
-                        (const void *)block_kernel<true, true>}) {
+                        (const void *)block_kernel<true, true>,
+                        (const void *)block_kernel<true, false, GRID_E2M1>,
+                        (const void *)block_kernel<true, true, GRID_E2M1>}) {
     if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
   }
   done = e == hipSuccess;
@@ -736,6 +818,11 @@ extern "C" size_t tg_quantize_workspace_size(int m, int n, int block) {
   return s.off + 256;
 }
 
+static int quantize_run(int grid, bool loop, void *stream, const float *W, int m, int n,
+                        const float *U, int k, int ldu, const int64_t *perm, const float *scale,
+                        const float *zero, int g, float minq, float maxq, int code_off, int block,
+                        float *Wq, uint8_t *codes, void *ws, size_t ws_bytes);
+
 static int gptq_quantize_impl(bool loop, void *stream, const float *W, int m, int n,
                               const float *U, int k, int ldu, const int64_t *perm,
                               const float *scale, const float *zero, int group, int w_bits,
@@ -755,6 +842,19 @@ static int gptq_quantize_impl(bool loop, void *stream, const float *W, int m, in
   TG_ARG(w_bits >= 2 && w_bits <= 8, 12, "w_bits must be in [2, 8]");
   TG_ARG(block >= 1 && block <= MAX_BLOCK, 14, "block_size must be in [1, 2048]");
   TG_ARG(Wq, 15, "null output");
+  const float minq = sym ? -float((1 << (w_bits - 1)) - 1) : 0.0f;
+  const float maxq = sym ? float((1 << (w_bits - 1)) - 1) : float((1 << w_bits) - 1);
+  const int code_off = sym ? (1 << (w_bits - 1)) : 0;
+  return quantize_run(GRID_INT, loop, stream, W, m, n, U, k, ldu, perm, scale, zero, g, minq, maxq,
+                      code_off, block, Wq, codes, ws, ws_bytes);
+}
+
+// The block loop behind tg_gptq_quantize / _loop (grid GRID_INT) and
+// tg_gptq_quantize_mx (GRID_E2M1: g = 32, zero unused); arguments checked.
+static int quantize_run(int grid, bool loop, void *stream, const float *W, int m, int n,
+                        const float *U, int k, int ldu, const int64_t *perm, const float *scale,
+                        const float *zero, int g, float minq, float maxq, int code_off, int block,
+                        float *Wq, uint8_t *codes, void *ws, size_t ws_bytes) {
   hipStream_t st = (hipStream_t)stream;
   TG_HIP(ensure_block_smem());
   tg::Arena ar(ws, ws_bytes);
@@ -762,9 +862,6 @@ static int gptq_quantize_impl(bool loop, void *stream, const float *W, int m, in
   quant_layout(ar, m, n, block, &q);
   TG_WS(ar);
   const int G = n / g;
-  const float minq = sym ? -float((1 << (w_bits - 1)) - 1) : 0.0f;
-  const float maxq = sym ? float((1 << (w_bits - 1)) - 1) : float((1 << w_bits) - 1);
-  const int code_off = sym ? (1 << (w_bits - 1)) : 0;
   const int bp = (block + 31) & ~31;
 
   hipLaunchKernelGGL(invperm_kernel, dim3(tg::cdiv(n, 256)), dim3(256), 0, st, perm, n, q.inv,
@@ -789,12 +886,17 @@ static int gptq_quantize_impl(bool loop, void *stream, const float *W, int m, in
     a.dbl = block_dbl(m);
     auto qtok = tg::prof_begin(st, tg::PROF_QBLOCK, 4.0 * 4.0 * double(m) * bw,
                                double(m) * bw * (bw - 1));
-    if (loop)
-      hipLaunchKernelGGL((block_kernel<true, true>), dim3(tg::cdiv(m, RW)), dim3(256),
-                         block_smem(bw, a.dbl), st, a);
-    else
-      hipLaunchKernelGGL((block_kernel<true, false>), dim3(tg::cdiv(m, RW)), dim3(256),
-                         block_smem(bw, a.dbl), st, a);
+#define TG_BLK(L_, G_)                                                              \
+  hipLaunchKernelGGL((block_kernel<true, L_, G_>), dim3(tg::cdiv(m, RW)), dim3(256), \
+                     block_smem(bw, a.dbl), st, a)
+    if (grid == GRID_E2M1) {
+      if (loop) TG_BLK(true, GRID_E2M1);
+      else TG_BLK(false, GRID_E2M1);
+    } else {
+      if (loop) TG_BLK(true, GRID_INT);
+      else TG_BLK(false, GRID_INT);
+    }
+#undef TG_BLK
     tg::prof_end(st, qtok);
     TG_LAUNCHED();
     if (nc > 0) {
@@ -811,9 +913,13 @@ static int gptq_quantize_impl(bool loop, void *stream, const float *W, int m, in
       TG_LAUNCHED();
     }
   }
-  hipLaunchKernelGGL(finalize_kernel, dim3(tg::cdiv(n, 256) < 16 ? tg::cdiv(n, 256) : 16, m),
-                     dim3(256), 0, st, q.Wp, q.Qp, q.cp, q.inv, q.perm32, scale, zero, G, g, n, k,
-                     minq, maxq, code_off, Wq, codes);
+  const dim3 fgrid(tg::cdiv(n, 256) < 16 ? tg::cdiv(n, 256) : 16, m);
+  if (grid == GRID_E2M1)
+    hipLaunchKernelGGL(finalize_kernel<GRID_E2M1>, fgrid, dim3(256), 0, st, q.Wp, q.Qp, q.cp, q.inv,
+                       q.perm32, scale, zero, G, g, n, k, minq, maxq, code_off, Wq, codes);
+  else
+    hipLaunchKernelGGL(finalize_kernel<GRID_INT>, fgrid, dim3(256), 0, st, q.Wp, q.Qp, q.cp, q.inv,
+                       q.perm32, scale, zero, G, g, n, k, minq, maxq, code_off, Wq, codes);
   TG_LAUNCHED();
   return 0;
 }
@@ -861,6 +967,57 @@ extern "C" int tg_pack_zeros(void *stream, const float *zero, int m, int G, int 
   const int off = sym ? (1 << (w_bits - 1)) : 0;
   hipLaunchKernelGGL(pack_zeros_kernel, dim3(tg::cdiv(nw, 256), G), dim3(256), 0,
                      (hipStream_t)stream, zero, m, G, w_bits, off, qzeros);
+  TG_LAUNCHED();
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
+// A15: MXFP4
+// ---------------------------------------------------------------------------
+extern "C" int tg_group_params_mx(void *stream, const float *W, int m, int n, int ldw, int fmt,
+                                  float *scale, uint8_t *e8m0) {
+  TG_ARG(W, 2, "null W");
+  TG_ARG(m > 0, 3, "m <= 0");
+  TG_ARG(n > 0 && n % MXG == 0, 4, "n must be a positive multiple of 32");
+  TG_ARG(ldw >= n, 5, "ldw < n");
+  TG_ARG(fmt == TG_FMT_MXFP4, 6, "fmt must be TG_FMT_MXFP4");
+  TG_ARG(scale, 7, "null scale");
+  TG_ARG(e8m0, 8, "null e8m0");
+  const int G = n / MXG;
+  const int64_t groups = int64_t(m) * G;
+  hipLaunchKernelGGL(mx_group_params_kernel, dim3(tg::cdiv(groups * MXG, 256)), dim3(256), 0,
+                     (hipStream_t)stream, W, ldw, G, groups, scale, e8m0);
+  TG_LAUNCHED();
+  return 0;
+}
+
+extern "C" int tg_gptq_quantize_mx(void *stream, const float *W, int m, int n, const float *U,
+                                   int k, int ldu, const int64_t *perm, const float *scale,
+                                   int fmt, int loop, int block, float *Wq, uint8_t *codes,
+                                   void *ws, size_t ws_bytes) {
+  TG_ARG(W, 2, "null W");
+  TG_ARG(m > 0, 3, "m <= 0");
+  TG_ARG(n > 0 && n % MXG == 0, 4, "n must be a positive multiple of 32");
+  TG_ARG(U, 5, "null U");
+  TG_ARG(k >= 1 && k <= n, 6, "rank k must be in [1, n]");
+  TG_ARG(ldu >= n, 7, "ldu < n");
+  TG_ARG(perm, 8, "null perm");
+  TG_ARG(scale, 9, "null scale");
+  TG_ARG(fmt == TG_FMT_MXFP4, 10, "fmt must be TG_FMT_MXFP4");
+  TG_ARG(loop == 0 || loop == 1, 11, "loop must be 0 or 1");
+  TG_ARG(block >= 1 && block <= MAX_BLOCK, 12, "block_size must be in [1, 2048]");
+  TG_ARG(Wq, 13, "null output");
+  return quantize_run(GRID_E2M1, loop != 0, stream, W, m, n, U, k, ldu, perm, scale, nullptr, MXG,
+                      0.0f, 0.0f, 0, block, Wq, codes, ws, ws_bytes);
+}
+
+extern "C" int tg_pack_e8m0(void *stream, const uint8_t *e8m0, int m, int G, uint8_t *out) {
+  TG_ARG(e8m0, 2, "null e8m0");
+  TG_ARG(m > 0, 3, "m <= 0");
+  TG_ARG(G > 0, 4, "G <= 0");
+  TG_ARG(out, 5, "null output");
+  hipLaunchKernelGGL(pack_e8m0_kernel, dim3(tg::cdiv(int64_t(m) * G, 256)), dim3(256), 0,
+                     (hipStream_t)stream, e8m0, m, G, out);
   TG_LAUNCHED();
   return 0;
 }

@@ -17,8 +17,16 @@ TruncGPTQ settings and per-layer ranks.  Dequantisation:
 W[:, j] = (code_u[:, j] - zero_u[:, g(j)]) * scale[:, g(j)], with symmetric
 codes stored +2^(b-1) (so zero_u = 2^(b-1)).
 
+MXFP4 (``weight_format="mxfp4"``; ``"checkpoint_format": "mxfp4"``, bits 4,
+group_size 32): per linear only
+  ``<name>.qweight`` int32 (in/8, out)    E2M1 codes, the same 4-bit stream,
+  ``<name>.scales``  uint8 (in/32, out)   E8M0 bytes, scale = 2^(byte - 127),
+and the bias; W[:, j] = +-{0, .5, 1, 1.5, 2, 3, 4, 6}[code & 7] * scale[:, j // 32],
+the sign in bit 3 of the code.
+
 ``load_quantized`` is the way back: it puts the packed tensors into
-``qlinear.QuantLinear`` modules of a model, which run them without unpacking.
+``qlinear.QuantLinear`` (``qlinear.MXQuantLinear`` for MXFP4) modules of a
+model, which run them without unpacking.
 """
 from __future__ import annotations
 
@@ -34,14 +42,30 @@ __all__ = ["save_quantized", "read_quantized", "load_quantized"]
 def save_quantized(path: str, model: torch.nn.Module, packed: Dict[str, Dict[str, torch.Tensor]],
                    w_bits: int, group_size: int, sym: bool,
                    extra_config: Optional[Dict[str, Any]] = None,
-                   scale_dtype: torch.dtype = torch.float16) -> str:
+                   scale_dtype: torch.dtype = torch.float16,
+                   weight_format: str = "int") -> str:
     """Write ``model.safetensors`` + ``quantize_config.json`` (+ ``config.json``
-    when the model has a HF config) into `path`; returns the tensor file path."""
+    when the model has a HF config) into `path`; returns the tensor file path.
+    ``weight_format="mxfp4"``: `packed` holds ``pack_quantized``'s MXFP4 pairs
+    (``qzeros`` None); `w_bits` must be 4 and `group_size` 32, `sym` and
+    `scale_dtype` are not used."""
     from safetensors.torch import save_file
+    if weight_format not in ("int", "mxfp4"):
+        raise ValueError(f"weight_format must be 'int' or 'mxfp4', got {weight_format!r}")
+    mx = weight_format == "mxfp4"
+    if mx and (int(w_bits) != 4 or int(group_size) != 32):
+        raise ValueError(f"weight_format='mxfp4' needs w_bits=4 and group_size=32, got "
+                         f"w_bits={w_bits}, group_size={group_size}")
     os.makedirs(path, exist_ok=True)
     sd = model.state_dict()
     tensors: Dict[str, torch.Tensor] = {}
     for name, t in packed.items():
+        if mx:
+            if t["scales"].dtype != torch.uint8:
+                raise ValueError(f"{name}: MXFP4 scales must be uint8, got {t['scales'].dtype}")
+            tensors[f"{name}.qweight"] = t["qweight"].contiguous().cpu()
+            tensors[f"{name}.scales"] = t["scales"].contiguous().cpu()
+            continue
         in_features = t["qweight"].shape[0] * 32 // w_bits
         g = group_size if group_size > 0 else in_features
         tensors[f"{name}.qweight"] = t["qweight"].contiguous().cpu()
@@ -66,6 +90,8 @@ def save_quantized(path: str, model: torch.nn.Module, packed: Dict[str, Dict[str
           "desc_act": False, "static_groups": True, "true_sequential": True,
           "quant_method": "gptq", "checkpoint_format": "gptq_v2",
           "scale_dtype": str(scale_dtype).replace("torch.", "")}
+    if mx:
+        qc.update(sym=True, checkpoint_format="mxfp4", scale_dtype="e8m0")
     if extra_config:
         qc["truncgptq"] = extra_config
     with open(os.path.join(path, "quantize_config.json"), "w") as f:
@@ -104,6 +130,8 @@ def load_quantized(model: torch.nn.Module, path: str, device=None) -> torch.nn.M
     from .qlinear import QuantLinear
     tensors, qc = read_quantized(path)
     bits, group = int(qc["bits"]), int(qc["group_size"])
+    if qc.get("checkpoint_format") == "mxfp4":
+        return _load_mx(model, tensors, qc, device)
     if bits not in (2, 3, 4, 8):
         raise ValueError(f"quantize_config.json: bits={bits} is not one of 2, 3, 4, 8")
     if qc.get("desc_act", False):
@@ -114,7 +142,7 @@ def load_quantized(model: torch.nn.Module, path: str, device=None) -> torch.nn.M
     fmt = qc.get("checkpoint_format", "gptq_v2")
     if fmt != "gptq_v2":
         raise ValueError(f"quantize_config.json: checkpoint_format={fmt!r}; only gptq_v2 (true "
-                         "zero points) is supported")
+                         "zero points) and mxfp4 are supported")
     names = [k[:-len(".qweight")] for k in tensors if k.endswith(".qweight")]
     used = set()
     for name in names:
@@ -144,6 +172,51 @@ def load_quantized(model: torch.nn.Module, path: str, device=None) -> torch.nn.M
                              f"model's linear is {lin.out_features} x {lin.in_features}")
         _set_submodule(model, name, q)
         used.update(v for v in keys.values() if v in tensors)
+    return _load_rest(model, tensors, used, device)
+
+
+def _load_mx(model: torch.nn.Module, tensors: Dict[str, torch.Tensor], qc: Dict[str, Any],
+             device) -> torch.nn.Module:
+    """load_quantized for ``checkpoint_format: "mxfp4"``: every ``nn.Linear``
+    with a ``<name>.qweight`` becomes a ``qlinear.MXQuantLinear``."""
+    from .qlinear import MXQuantLinear
+    if int(qc["bits"]) != 4 or int(qc["group_size"]) != 32:
+        raise ValueError(f"quantize_config.json: mxfp4 needs bits=4 and group_size=32, got "
+                         f"bits={qc['bits']}, group_size={qc['group_size']}")
+    if qc.get("desc_act", False):
+        raise ValueError("quantize_config.json: desc_act=true (act-order) checkpoints are not "
+                         "supported")
+    used = set()
+    for name in [k[:-len(".qweight")] for k in tensors if k.endswith(".qweight")]:
+        try:
+            lin = model.get_submodule(name)
+        except AttributeError:
+            raise KeyError(f"{name}: packed in the checkpoint but absent from the model") from None
+        if not isinstance(lin, torch.nn.Linear):
+            raise TypeError(f"{name}: expected nn.Linear, found {type(lin).__name__}")
+        keys = {k: f"{name}.{k}" for k in ("qweight", "scales", "bias")}
+        if keys["scales"] not in tensors:
+            raise KeyError(f"{keys['scales']} is missing from the checkpoint")
+        bias = tensors.get(keys["bias"])
+        if (bias is None) != (lin.bias is None):
+            raise ValueError(f"{name}: the checkpoint and the model disagree about a bias")
+        if bias is not None:
+            bias = bias.to(lin.bias.dtype)
+        try:
+            q = MXQuantLinear.from_packed(tensors[keys["qweight"]], tensors[keys["scales"]],
+                                          bias=bias, device=lin.weight.device)
+        except ValueError as e:
+            raise ValueError(f"{name}: {e}") from None
+        if (q.out_features, q.in_features) != (lin.out_features, lin.in_features):
+            raise ValueError(f"{name}: packed weight is {q.out_features} x {q.in_features}, the "
+                             f"model's linear is {lin.out_features} x {lin.in_features}")
+        _set_submodule(model, name, q)
+        used.update(v for v in keys.values() if v in tensors)
+    return _load_rest(model, tensors, used, device)
+
+
+def _load_rest(model: torch.nn.Module, tensors: Dict[str, torch.Tensor], used, device):
+    """Every tensor the packed modules did not take, loaded as is."""
     rest = {k: v for k, v in tensors.items() if k not in used}
     missing, unexpected = model.load_state_dict(rest, strict=False)
     missing = [k for k in missing if k not in used]

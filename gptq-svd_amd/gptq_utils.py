@@ -425,11 +425,31 @@ class Quantizer:
     tg_group_params_clip.  i = 0 is the plain min/max (absmax) choice, so the
     weighted error never rises.  ``clip_choice`` (m, n/g int32) and
     ``clip_objective`` (m, n/g, 2 float64: {J_0, J_chosen}) hold the last
-    search's results."""
+    search's results.
+
+    ``weight_format="mxfp4"`` (A15, new): OCP Microscaling FP4 instead of the
+    uniform integer grid -- E2M1 elements {0, .5, 1, 1.5, 2, 3, 4, 6} with a
+    sign, one power-of-two scale 2^E per 32 columns, E = max(floor(log2 max|w|)
+    - 2, -126) (the contract is in include/truncgptq.h).  It needs w_bits = 4
+    and group_size = 32 and has no clip search.  ``find_params`` then fills
+    ``scale`` (m, n/32, 1) with 2^E, ``zero`` with zeros and ``scale_e8m0``
+    (m, n/32) uint8 with the stored bytes E + 127."""
 
     def __init__(self, w_bits: int = 4, group_size: int = 128, sym: bool = False,
                  clip_search: bool = False, clip_grid: int = 100, clip_steps: int = 80,
-                 col_weight: Optional[torch.Tensor] = None):
+                 col_weight: Optional[torch.Tensor] = None, weight_format: str = "int"):
+        if weight_format not in ("int", "mxfp4"):
+            raise ValueError(f"Quantizer: weight_format must be 'int' or 'mxfp4', got "
+                             f"{weight_format!r}")
+        if weight_format == "mxfp4":
+            if w_bits != 4 or group_size != 32:
+                raise ValueError(f"Quantizer: weight_format='mxfp4' needs w_bits=4 and "
+                                 f"group_size=32, got w_bits={w_bits}, group_size={group_size}")
+            if clip_search:
+                raise ValueError("Quantizer: clip_search is not defined for "
+                                 "weight_format='mxfp4'")
+        self.weight_format = weight_format
+        self.scale_e8m0 = None
         self.w_bits = w_bits
         self.group_size = group_size
         self.sym = sym
@@ -460,6 +480,15 @@ class Quantizer:
         W = weights.to(torch.float32).contiguous()
         G = n // g
         scale = torch.empty((m, G), dtype=torch.float32, device=W.device)
+        if self.weight_format == "mxfp4":
+            e8m0 = torch.empty((m, G), dtype=torch.uint8, device=W.device)
+            with torch.cuda.device(W.device):
+                call("tg_group_params_mx", stream(), ptr(W), m, n, n, _lib.TG_FMT_MXFP4,
+                     ptr(scale), ptr(e8m0))
+            self.scale = scale.unsqueeze(-1)
+            self.zero = torch.zeros_like(self.scale)
+            self.scale_e8m0 = e8m0
+            return
         zero = torch.empty((m, G), dtype=torch.float32, device=W.device)
         if self.clip_search:
             h = self.col_weight
@@ -565,6 +594,8 @@ def gptq_fwrd(weight_mat: torch.Tensor, H_inv_sqrt: torch.Tensor, quantizer: Qua
     round-half-even, error divided by U[c, c], raw U rows for propagation.
     The integer codes of the last call are kept on ``quantizer.codes``
     (uint8, original order, +2^(b-1) offset when sym) for packing.
+    A ``Quantizer(weight_format="mxfp4")`` runs the same two procedures on the
+    E2M1 grid (tg_gptq_quantize_mx); its codes are the 4-bit E2M1 codes.
     """
     allow_tf32 = torch.backends.cuda.matmul.allow_tf32       # :474-475, restored :565
     torch.backends.cuda.matmul.allow_tf32 = False
@@ -587,11 +618,17 @@ def gptq_fwrd(weight_mat: torch.Tensor, H_inv_sqrt: torch.Tensor, quantizer: Qua
         with torch.cuda.device(device):
             ws = workspace(_lib.lib.tg_quantize_workspace_size(out_features, in_features,
                                                                block_size), device)
-            call("tg_gptq_quantize" if use_triton else "tg_gptq_quantize_loop", stream(),
-                 ptr(weight_mat), out_features, in_features,
-                 ptr(U), current_rank, U.shape[1], ptr(perm_d), ptr(scale), ptr(zero),
-                 quantizer.group_size, quantizer.w_bits, int(quantizer.sym), block_size,
-                 ptr(Wq), ptr(codes), ptr(ws), ws.numel())
+            if getattr(quantizer, "weight_format", "int") == "mxfp4":
+                call("tg_gptq_quantize_mx", stream(), ptr(weight_mat), out_features, in_features,
+                     ptr(U), current_rank, U.shape[1], ptr(perm_d), ptr(scale),
+                     _lib.TG_FMT_MXFP4, 0 if use_triton else 1, block_size, ptr(Wq), ptr(codes),
+                     ptr(ws), ws.numel())
+            else:
+                call("tg_gptq_quantize" if use_triton else "tg_gptq_quantize_loop", stream(),
+                     ptr(weight_mat), out_features, in_features,
+                     ptr(U), current_rank, U.shape[1], ptr(perm_d), ptr(scale), ptr(zero),
+                     quantizer.group_size, quantizer.w_bits, int(quantizer.sym), block_size,
+                     ptr(Wq), ptr(codes), ptr(ws), ws.numel())
         quantizer.codes = codes
         if R_x is not None:
             log_quantization_error(weight_mat, Wq, R_x, perm_d)
@@ -606,10 +643,22 @@ def gptq_fwrd(weight_mat: torch.Tensor, H_inv_sqrt: torch.Tensor, quantizer: Qua
 def pack_quantized(quantizer: Quantizer, codes: Optional[torch.Tensor] = None):
     """AutoGPTQ-style tensors from the last gptq_fwrd: qweight int32
     (n*b/32, m), qzeros int32 (n/g, m*b/32), scales float32 (n/g, m).
-    Static groups in original column order, so no g_idx is needed."""
+    Static groups in original column order, so no g_idx is needed.
+    For ``weight_format="mxfp4"``: (qweight, None, scales) with qweight the same
+    4-bit stream of the E2M1 codes and scales the E8M0 bytes, uint8 (n/32, m)."""
     codes = quantizer.codes if codes is None else codes
     m, n = codes.shape
     b = quantizer.w_bits
+    if getattr(quantizer, "weight_format", "int") == "mxfp4":
+        dev = codes.device
+        e8m0 = quantizer.scale_e8m0.contiguous()
+        G = e8m0.shape[1]
+        qweight = torch.empty((n * 4 // 32, m), dtype=torch.int32, device=dev)
+        scales = torch.empty((G, m), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            call("tg_pack_codes", stream(), ptr(codes.contiguous()), m, n, 4, ptr(qweight))
+            call("tg_pack_e8m0", stream(), ptr(e8m0), m, G, ptr(scales))
+        return qweight, None, scales
     zero = quantizer.zero.squeeze(-1).contiguous()
     G = zero.shape[1]
     dev = codes.device

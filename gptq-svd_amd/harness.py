@@ -334,7 +334,8 @@ def quantize_model(model: nn.Module, input_ids_list: Sequence[torch.Tensor], mod
                    run_config: Optional[Dict[str, Any]] = None,
                    staged: Optional[bool] = None, sketch_ratio: float = 4.0,
                    sketch_seed: Optional[int] = None, clip_search: bool = False,
-                   clip_grid: int = 100, clip_steps: int = 80) -> Dict[str, Any]:
+                   clip_grid: int = 100, clip_steps: int = 80,
+                   weight_format: str = "int") -> Dict[str, Any]:
     """Quantise every sequenced linear of `model` in place (layer by layer).
 
     mode "eigh" = TruncGPTQ (process_hessian_alt + gptq_fwrd(use_triton=True));
@@ -356,6 +357,15 @@ def quantize_model(model: nn.Module, input_ids_list: Sequence[torch.Tensor], mod
     Each module logs its weighted round-to-nearest error before and after and
     the number of groups the search moved, and its ``layer_stats`` entry
     carries them (``clip_j0``, ``clip_j``, ``clip_moved``, ``clip_groups``).
+    `weight_format` (A15): "int" (default) is the uniform integer grid of
+    `w_bits` / `group_size` / `sym`; "mxfp4" quantises onto OCP Microscaling FP4
+    (E2M1 elements, one power-of-two scale per 32 input columns) with the same
+    error propagation, in modes "eigh", "svd" and "gptq".  It fixes `w_bits` = 4
+    and `group_size` = 32 (whatever was passed; `sym` is not used), cannot be
+    combined with `clip_search` or the multi-GPU mode (ValueError before any
+    work), and with ``pack=True`` keeps ``qweight`` and the uint8 ``scales`` of
+    each linear (``qzeros`` None).  Every ``layer_stats`` entry records the
+    format.
     `offload`: move each layer to `device` for its turn and back to the CPU
     afterwards (the reference's policy, quantize.py:101, :239); by default
     the model stays where it is (a whole 8B/70B model fits in 288 GB).
@@ -385,6 +395,16 @@ def quantize_model(model: nn.Module, input_ids_list: Sequence[torch.Tensor], mod
         raise ValueError(f"mode must be 'eigh', 'gptq' or 'svd', got {mode!r}")
     if mode == "svd" and _world(pg)[0] > 1:
         raise ValueError("mode 'svd' is single-process")
+    if weight_format not in ("int", "mxfp4"):
+        raise ValueError(f"weight_format must be 'int' or 'mxfp4', got {weight_format!r}")
+    if weight_format == "mxfp4":
+        if clip_search:
+            raise ValueError("weight_format='mxfp4' cannot be combined with clip_search")
+        if _world(pg)[0] > 1:
+            raise ValueError("weight_format='mxfp4' is single-process")
+        w_bits, group_size = 4, 32
+    # passed on only for MX, so an integer run is unchanged
+    fmt_kw = dict(weight_format=weight_format) if weight_format != "int" else {}
     if not 0 <= clip_steps < clip_grid:
         raise ValueError(f"need 0 <= clip_steps < clip_grid, got clip_steps={clip_steps}, "
                          f"clip_grid={clip_grid}")
@@ -399,7 +419,7 @@ def quantize_model(model: nn.Module, input_ids_list: Sequence[torch.Tensor], mod
                              batch_size=batch_size, device=device, block_size=block_size,
                              pack=pack, offload=offload, pg=pg, early_stop=early_stop, clock=clock,
                              staged=staged, sketch_ratio=sketch_ratio, sketch_seed=sketch_seed,
-                             **clip_kw)
+                             **clip_kw, **fmt_kw)
         return res
     t_start = time.time()
     world, rank = _world(pg)
@@ -481,7 +501,7 @@ def quantize_model(model: nn.Module, input_ids_list: Sequence[torch.Tensor], mod
             R_x = None
         if clock:
             clock.stop(f"factor_n{H.shape[1]}", ev)
-        qkw = dict(clip_kw)
+        qkw = dict(clip_kw, **fmt_kw)
         if clip_search:
             # the search's column weights, taken before H is freed
             qkw["col_weight"] = (H.float().square().sum(dim=0) if mode == "svd"
@@ -512,6 +532,8 @@ def quantize_model(model: nn.Module, input_ids_list: Sequence[torch.Tensor], mod
             used = k if mode != "gptq" else "N/A"
             logging.info(f"   {name: <15} | Rank: {str(used): <4} | Time: {dt:.2f}s")
             entry = {"name": full, "rank": used, "time": dt}
+            if fmt_kw:
+                entry["weight_format"] = weight_format
             if clip_search:
                 j0, j1 = q.clip_objective.sum(dim=(0, 1)).tolist()
                 moved = int((q.clip_choice != 0).sum().item())
@@ -670,6 +692,8 @@ def run_and_record(model: nn.Module, input_ids_list: Sequence[torch.Tensor], sav
         cfg["sketch_seed"] = kw.get("sketch_seed")
     if kw.get("clip_search"):
         cfg.update(_clip_settings(kw))
+    if kw.get("weight_format", "int") != "int":
+        cfg.update(weight_format=kw["weight_format"], w_bits=4, group_size=32)
     mid = getattr(getattr(model, "config", None), "_name_or_path", None)
     if mid:
         cfg["model_id"] = mid
@@ -712,9 +736,13 @@ def _packed_copy(model: nn.Module, res: Dict[str, Any], save_path: str,
     extra = {"mode": kw.get("mode", "eigh")}
     if kw.get("clip_search"):
         extra.update(_clip_settings(kw))
-    save_quantized(path, model, res["packed"], int(kw.get("w_bits", 4)),
-                   int(kw.get("group_size", -1)), bool(kw.get("sym", False)),
-                   extra_config=extra)
+    if kw.get("weight_format", "int") == "mxfp4":
+        save_quantized(path, model, res["packed"], 4, 32, True, extra_config=extra,
+                       weight_format="mxfp4")
+    else:
+        save_quantized(path, model, res["packed"], int(kw.get("w_bits", 4)),
+                       int(kw.get("group_size", -1)), bool(kw.get("sym", False)),
+                       extra_config=extra)
     twin = copy.deepcopy(model)
     if next(twin.parameters()).dtype == torch.float32:
         twin = twin.half()

@@ -11,6 +11,13 @@ Layout (export.py): ``qweight`` int32 (in*b/32, out), ``qzeros`` int32
 (G, out*b/32), ``scales`` fp16 or fp32 (G, out), ``g_idx`` int32 (in,) -- only
 the trivial map ``arange(in) // group`` (static groups, original column
 order).  w = (code_u - zero_u) * scale.
+
+MXFP4 checkpoints (``checkpoint_format: "mxfp4"``) hold ``qweight`` int32
+(in/8, out), the same 4-bit stream of E2M1 codes, and ``scales`` uint8
+(in/32, out), the E8M0 byte of each group of 32 input columns; no ``qzeros``
+and no ``g_idx``.  w = +-{0, .5, 1, 1.5, 2, 3, 4, 6}[code & 7] * 2^(byte - 127).
+``dequantize_packed_mx`` and ``MXQuantLinear`` are their consumers
+(``tg_dequant_mx``, ``tg_qgemm_mx``).
 """
 from __future__ import annotations
 
@@ -19,9 +26,9 @@ from typing import Optional
 import torch
 from torch import nn
 
-from ._lib import DTYPES, call, lib, ptr, require_cuda, stream, workspace
+from ._lib import DTYPES, TG_FMT_MXFP4, call, lib, ptr, require_cuda, stream, workspace
 
-__all__ = ["QuantLinear", "dequantize_packed"]
+__all__ = ["QuantLinear", "dequantize_packed", "MXQuantLinear", "dequantize_packed_mx"]
 
 _BITS = (2, 3, 4, 8)
 
@@ -159,6 +166,123 @@ class QuantLinear(nn.Module):
                 call("tg_qgemm", stream(), ptr(x2), DTYPES[x.dtype], T, ldx, ptr(self.qweight),
                      ptr(self.qzeros), ptr(self.scales), DTYPES[self.scales.dtype], m, n,
                      self.group_size, self.w_bits, ptr(bias),
+                     DTYPES[bias.dtype] if bias is not None else 0, ptr(y), DTYPES[x.dtype], m,
+                     ptr(ws), nbytes)
+        return y.reshape(*x.shape[:-1], m)
+
+
+# ---------------------------------------------------------------------------
+# MXFP4 (A15)
+# ---------------------------------------------------------------------------
+def _shapes_mx(qweight: torch.Tensor, scales: torch.Tensor):
+    """(m, n) of an MXFP4 pair, checked against each other."""
+    if qweight.dtype != torch.int32:
+        raise ValueError("qweight must be int32")
+    if scales.dtype != torch.uint8:
+        raise ValueError(f"MXFP4 scales must be uint8 (E8M0 bytes), got {scales.dtype}")
+    if qweight.dim() != 2 or scales.dim() != 2:
+        raise ValueError("qweight and scales must be matrices")
+    nw, m = qweight.shape
+    n = nw * 8
+    if n % 32 or (m * 4) % 32:
+        raise ValueError(f"MXFP4 needs in_features % 32 == 0 and out_features % 8 == 0 (got "
+                         f"in={n}, out={m})")
+    if tuple(scales.shape) != (n // 32, m):
+        raise ValueError(f"packed shapes disagree: qweight {tuple(qweight.shape)}, scales "
+                         f"{tuple(scales.shape)} (expected {(n // 32, m)})")
+    return m, n
+
+
+def dequantize_packed_mx(qweight: torch.Tensor, scales: torch.Tensor,
+                         dtype: torch.dtype = torch.float16) -> torch.Tensor:
+    """Dense weight (out, in) of `dtype` (fp16 / bf16 / fp32) of an MXFP4 pair:
+    ``grid[code] * 2^(byte - 127)`` rounded once to `dtype`.  fp16 overflows to
+    inf for scale bytes from 141 up; bf16 and fp32 cover every byte."""
+    m, n = _shapes_mx(qweight, scales)
+    for t, what in ((qweight, "qweight"), (scales, "scales")):
+        require_cuda(t, what)
+    if dtype not in (torch.float16, torch.bfloat16, torch.float32):
+        raise ValueError(f"dtype must be float16, bfloat16 or float32, got {dtype}")
+    dev = qweight.device
+    qweight, scales = qweight.contiguous(), scales.contiguous()
+    out = torch.empty((m, n), dtype=dtype, device=dev)
+    with torch.cuda.device(dev):
+        call("tg_dequant_mx", stream(), ptr(qweight), ptr(scales), TG_FMT_MXFP4, m, n, ptr(out),
+             DTYPES[dtype], n)
+    return out
+
+
+class MXQuantLinear(nn.Module):
+    """A linear layer whose weight stays packed as MXFP4: buffers ``qweight``
+    int32 (in/8, out) and ``scales`` uint8 (in/32, out), the checkpoint's keys.
+    Weights only: activations are fp16 / bf16 and the decoded weight feeds the
+    16-bit kernels of ``QuantLinear`` (``tg_qgemm_mx``)."""
+
+    w_bits, group_size = 4, 32
+
+    def __init__(self, in_features: int, out_features: int, bias: bool = False,
+                 bias_dtype: torch.dtype = torch.float16, device=None):
+        super().__init__()
+        if in_features % 32 or (out_features * 4) % 32:
+            raise ValueError(f"MXQuantLinear needs in_features % 32 == 0 and out_features % 8 == 0 "
+                             f"(got in={in_features}, out={out_features})")
+        self.in_features, self.out_features = int(in_features), int(out_features)
+        self.register_buffer("qweight", torch.zeros((in_features // 8, out_features),
+                                                    dtype=torch.int32, device=device))
+        # byte 127 = scale 1
+        self.register_buffer("scales", torch.full((in_features // 32, out_features), 127,
+                                                  dtype=torch.uint8, device=device))
+        if bias:
+            self.register_buffer("bias", torch.zeros(out_features, dtype=bias_dtype, device=device))
+        else:
+            self.bias = None
+
+    @classmethod
+    def from_packed(cls, qweight: torch.Tensor, scales: torch.Tensor,
+                    bias: Optional[torch.Tensor] = None, device=None) -> "MXQuantLinear":
+        """From the packed pair (a checkpoint's, or ``pack_quantized``'s)."""
+        m, n = _shapes_mx(qweight, scales)
+        dev = device if device is not None else qweight.device
+        q = cls(n, m, bias=bias is not None,
+                bias_dtype=bias.dtype if bias is not None else torch.float16, device=dev)
+        q.qweight.copy_(qweight)
+        q.scales.copy_(scales)
+        if bias is not None:
+            q.bias.copy_(bias.detach())
+        return q
+
+    def extra_repr(self) -> str:
+        return (f"in_features={self.in_features}, out_features={self.out_features}, "
+                f"format=mxfp4, bias={self.bias is not None}")
+
+    def dequantize(self, dtype: torch.dtype = torch.float16) -> torch.Tensor:
+        """The dense (out, in) weight."""
+        return dequantize_packed_mx(self.qweight, self.scales, dtype)
+
+    @torch.no_grad()
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        require_cuda(x, "MXQuantLinear input")
+        require_cuda(self.qweight, "MXQuantLinear.qweight")
+        if x.dtype not in (torch.float16, torch.bfloat16):
+            raise RuntimeError(f"MXQuantLinear takes float16 or bfloat16 activations, got "
+                               f"{x.dtype} (there is no fp32 kernel and no fallback)")
+        if x.shape[-1] != self.in_features:
+            raise RuntimeError(f"MXQuantLinear: last dim {x.shape[-1]} != in_features "
+                               f"{self.in_features}")
+        n, m = self.in_features, self.out_features
+        x2 = x.reshape(-1, n)
+        T = x2.shape[0]
+        y = torch.empty((T, m), dtype=x.dtype, device=x.device)
+        if T > 0:
+            if x2.stride(1) != 1 or (T > 1 and x2.stride(0) < n):
+                x2 = x2.contiguous()
+            ldx = x2.stride(0) if T > 1 else n
+            bias = self.bias
+            with torch.cuda.device(x.device):
+                nbytes = lib.tg_qgemm_workspace_size(T, m, n)
+                ws = workspace(nbytes, x.device)
+                call("tg_qgemm_mx", stream(), ptr(x2), DTYPES[x.dtype], T, ldx, ptr(self.qweight),
+                     ptr(self.scales), TG_FMT_MXFP4, m, n, ptr(bias),
                      DTYPES[bias.dtype] if bias is not None else 0, ptr(y), DTYPES[x.dtype], m,
                      ptr(ws), nbytes)
         return y.reshape(*x.shape[:-1], m)

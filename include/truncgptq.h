@@ -435,6 +435,77 @@ int tg_qgemm(void *stream, const void *X, int x_dtype, int T, int64_t ldx, const
              int w_bits, const void *bias, int bias_dtype, void *Y, int y_dtype, int64_t ldy,
              void *ws, size_t ws_bytes);
 
+/* ---- A15: MXFP4 weight format (new; OCP Microscaling FP4) ------------------
+ * E2M1 elements, one shared E8M0 power-of-two scale per 32 values.  `fmt` is a
+ * tg_weight_format; TG_FMT_MXFP4 is its only value (anything else is rejected
+ * with fmt's argument index).  Every f32 operation below is one correctly
+ * rounded operation in the order written, no contraction.  Weights are finite;
+ * NaN and Inf are outside the contract.
+ *
+ * Groups: 32 consecutive columns in the original column order, per row;
+ * n % 32 == 0.  Static groups, gathered through perm like the integer scales.
+ *
+ * Scale (tg_group_params_mx; W m x n f32 with row stride stride_w >= n, both
+ * outputs m x n/32): a = max |w| over the group; e = floor(log2 a),
+ * the unbiased exponent (subnormals: their true floor(log2); a == 0: -inf);
+ * E = max(e - 2, -126), 2 being E2M1's emax; E <= 125 for finite a.
+ * scale = 2^E, always a normal f32; the stored byte is E + 127, in [1, 252]:
+ * byte 255 (NaN) is never written.
+ *
+ * Element: t = w / scale, m = |t|,
+ *   idx = (m > 0.25) + (m >= 0.75) + (m > 1.25) + (m >= 1.75) + (m > 2.5)
+ *       + (m >= 3.5) + (m > 5)
+ * indexes {0, 0.5, 1, 1.5, 2, 3, 4, 6}: round to nearest, ties to the even
+ * code, saturating at 6.  code = idx | (8 if t < 0 and idx != 0 else 0): code 8
+ * (-0) is never produced.  qv = +-grid[idx] * scale, +0 for idx == 0.  The
+ * kernels multiply by the exactly representable 2^-E instead of dividing, which
+ * is bit-identical.
+ *
+ * tg_gptq_quantize_mx: tg_gptq_quantize (loop = 0: err = w - qv) or
+ * tg_gptq_quantize_loop (loop = 1: err = (w - qv) / U[c, c]) with the element
+ * rule in place of the integer rule, in the column chain and in the tail beyond
+ * rank k; everything else (separately rounded mul and sub in panel order, the
+ * k-ordered fmaf chain across blocks, the unpermute) as there.  scale is
+ * tg_group_params_mx's (m x n/32 f32), U is k x n with row stride stride_u;
+ * codes (m x n uint8, values 0..15 except 8, original column order; nullable).
+ * Workspace: tg_quantize_workspace_size.
+ *
+ * Packed image: qweight = tg_pack_codes(w_bits = 4) of those codes;
+ * tg_pack_e8m0 transposes the scale bytes (m x G) into (G x m), which the
+ * consumers read coalesced.
+ *
+ * Decode (tg_dequant_mx, and the weight operand of tg_qgemm_mx):
+ * float(+-grid[code & 7]) * ldexpf(1, byte - 127), one f32 multiply, then one
+ * round-to-nearest-even to the output / operand type.  Bytes 0 .. 254 all
+ * decode (byte 0 is the subnormal 2^-127).  fp16 overflows to inf from 6 * 2^14
+ * up (byte >= 141) and flushes small scales to zero; bf16 covers the range.
+ * In fp32 the values 4 and 6 overflow from byte 253 up (6 * 2^125, byte 252, the
+ * largest the solver writes, is finite).  out: m x n (row stride stride_o >= n),
+ * out_dtype TG_F16 / TG_BF16 / TG_F32.  Requires n % 32 == 0 and
+ * (m * 4) % 32 == 0.
+ *
+ * tg_qgemm_mx: tg_qgemm on that operand: Y (T x m) = X (T x n) * W^T (+ bias),
+ * the weight operand exactly tg_dequant_mx's output in x_dtype, products and
+ * sums f32, the bias added in f32, one rounding, bit-identical from call to
+ * call.  The same two regimes, the same TG_QGEMM switch, the same workspace
+ * (tg_qgemm_workspace_size) and the same argument checks as tg_qgemm; stride_x
+ * >= n and stride_y >= m are the row strides of X and Y.
+ * Weights only: activations stay 16-bit and the block-scaled MFMA
+ * instructions, which need both operands in low precision, are not used. */
+enum tg_weight_format { TG_FMT_MXFP4 = 1 };
+int tg_group_params_mx(void *stream, const float *W, int m, int n, int stride_w, int fmt,
+                       float *scale, uint8_t *e8m0);
+int tg_gptq_quantize_mx(void *stream, const float *W, int m, int n, const float *U, int k,
+                        int stride_u, const int64_t *perm, const float *scale, int fmt, int loop,
+                        int block, float *Wq, uint8_t *codes, void *ws, size_t ws_bytes);
+int tg_pack_e8m0(void *stream, const uint8_t *e8m0, int m, int G, uint8_t *out);
+int tg_dequant_mx(void *stream, const int32_t *qweight, const uint8_t *scales_e8m0, int fmt, int m,
+                  int n, void *out, int out_dtype, int64_t stride_o);
+int tg_qgemm_mx(void *stream, const void *X, int x_dtype, int T, int64_t stride_x,
+                const int32_t *qweight, const uint8_t *scales_e8m0, int fmt, int m, int n,
+                const void *bias, int bias_dtype, void *Y, int y_dtype, int64_t stride_y, void *ws,
+                size_t ws_bytes);
+
 #ifdef __cplusplus
 }
 #endif

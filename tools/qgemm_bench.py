@@ -11,10 +11,14 @@ bracket is long enough to time; the time of a call is the bracket over COPIES.
 Reported: the median of --runs runs after --warmup warm-up runs, and for the
 packed path the achieved GB/s of packed bytes (qweight + qzeros + scales).
 
+--format mxfp4 times tg_qgemm_mx on an MXFP4 image instead (E2M1 codes, one
+E8M0 byte per 32 values: the same bytes per weight as int4 at --group 32, the
+comparison that isolates the decode); --group sets the integer group size.
+
 --graph replays a captured graph of the same calls, so that the host's launch
 cost (which bounds the eager T = 1 numbers) is not in the bracket.
 
-    python tools/qgemm_bench.py [--graph] [--out profiles/qlinear/qgemm.json]
+    python tools/qgemm_bench.py [--graph] [--format int|mxfp4] [--group G] [--out FILE]
 """
 import argparse
 import json
@@ -29,16 +33,20 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 from gptq_svd_amd import _lib as L  # noqa: E402
-from gptq_svd_amd.qlinear import dequantize_packed  # noqa: E402
+from gptq_svd_amd.qlinear import dequantize_packed, dequantize_packed_mx  # noqa: E402
 
 DEV = "cuda:0"
 BITS, GROUP = 4, 128
 
 
-def random_packed(m, n, gen):
-    """Random words are random codes: every bit pattern is a valid stream."""
+def random_packed(m, n, gen, fmt="int"):
+    """Random words are random codes: every bit pattern is a valid stream.
+    mxfp4: (qweight, None, scale bytes 110 .. 125, i.e. scales 2^-17 .. 2^-2)."""
     qw = torch.randint(-2 ** 31, 2 ** 31 - 1, (n * BITS // 32, m), generator=gen,
                        dtype=torch.int64).to(torch.int32).to(DEV)
+    if fmt == "mxfp4":
+        return qw, None, torch.randint(110, 126, (n // 32, m), generator=gen,
+                                       dtype=torch.uint8).to(DEV)
     qz = torch.randint(-2 ** 31, 2 ** 31 - 1, (n // GROUP, m * BITS // 32), generator=gen,
                        dtype=torch.int64).to(torch.int32).to(DEV)
     sc = (torch.rand(n // GROUP, m, generator=gen) * 0.01 + 0.002).to(torch.float16).to(DEV)
@@ -77,6 +85,7 @@ def timed(fn, copies, flush, warmup, runs, graph=False):
 
 
 def main():
+    global GROUP
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "qlinear", "qgemm.json"))
     ap.add_argument("--runs", type=int, default=25)
@@ -84,7 +93,11 @@ def main():
     ap.add_argument("--T", type=int, nargs="+", default=[1, 8, 64, 512])
     ap.add_argument("--graph", action="store_true",
                     help="time a captured graph of the calls instead of eager launches")
+    ap.add_argument("--format", choices=["int", "mxfp4"], default="int")
+    ap.add_argument("--group", type=int, default=GROUP, help="integer group size (format int)")
     args = ap.parse_args()
+    mx = args.format == "mxfp4"
+    GROUP = 32 if mx else args.group
     if not torch.cuda.is_available():
         raise SystemExit("qgemm_bench needs the GPU (there is nothing to time without one)")
     gen = torch.Generator().manual_seed(0)
@@ -92,12 +105,17 @@ def main():
     forced = os.environ.get("TG_QGEMM") if os.environ.get("TG_QGEMM") in ("gemv", "mfma") else None
     rows = []
     for m, n in ((4096, 4096), (12288, 4096)):
-        qw, qz, sc = random_packed(m, n, gen)
-        dense = dequantize_packed(qw, qz, sc, BITS, GROUP, torch.float16)
-        packed_bytes = qw.numel() * 4 + qz.numel() * 4 + sc.numel() * 2
+        qw, qz, sc = random_packed(m, n, gen, args.format)
+        if mx:
+            dense = dequantize_packed_mx(qw, sc, torch.float16)
+            packed_bytes = qw.numel() * 4 + sc.numel()
+        else:
+            dense = dequantize_packed(qw, qz, sc, BITS, GROUP, torch.float16)
+            packed_bytes = qw.numel() * 4 + qz.numel() * 4 + sc.numel() * 2
         pc = -(-ROTATE_BYTES // packed_bytes)
         dc = -(-ROTATE_BYTES // (dense.numel() * 2))
-        packs = [(qw, qz, sc)] + [(qw.clone(), qz.clone(), sc.clone()) for _ in range(pc - 1)]
+        packs = [(qw, qz, sc)] + [(qw.clone(), None if mx else qz.clone(), sc.clone())
+                                  for _ in range(pc - 1)]
         denses = [dense] + [dense.clone() for _ in range(dc - 1)]
         for T in args.T:
             x = torch.randn(T, n, generator=gen).to(torch.float16).to(DEV)
@@ -107,6 +125,10 @@ def main():
 
             def packed_call(i):
                 a, b, c = packs[i]
+                if mx:
+                    L.call("tg_qgemm_mx", L.stream(), L.ptr(x), L.TG_F16, T, n, L.ptr(a), L.ptr(c),
+                           L.TG_FMT_MXFP4, m, n, None, 0, L.ptr(y), L.TG_F16, m, L.ptr(ws), nbytes)
+                    return
                 L.call("tg_qgemm", L.stream(), L.ptr(x), L.TG_F16, T, n, L.ptr(a), L.ptr(b),
                        L.ptr(c), L.TG_F16, m, n, GROUP, BITS, None, 0, L.ptr(y), L.TG_F16, m,
                        L.ptr(ws), nbytes)
@@ -127,7 +149,8 @@ def main():
                        max_rel_diff_vs_dense=rel)
             rows.append(row)
             print(json.dumps(row), flush=True)
-    out = dict(device=torch.cuda.get_device_name(0), bits=BITS, group=GROUP, dtype="float16",
+    out = dict(device=torch.cuda.get_device_name(0), format=args.format, bits=BITS, group=GROUP,
+               dtype="float16",
                runs=args.runs, warmup=args.warmup, launch="graph" if args.graph else "eager",
                method="HIP events around one call on each of >= 768 MB of weight copies, "
                       "per-call median; 1 GiB overwritten before every run",
