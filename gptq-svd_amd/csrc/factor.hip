@@ -56,7 +56,7 @@ struct PivWs {
   double *bc;    // PPS          last arriver's broadcast (pivot, its L row, swap)
   unsigned *flag;
   // candidate-set pivoting (piv_sel_kernel / piv_fill_kernel)
-  int32_t *sstate;  // [0] steps done, [1] steps of the last panel
+  int32_t *sstate;  // [0] steps done, [1] steps of the last panel, [2..] level words (SS_*)
   int32_t *prow;    // PB  pivot rows of the panel
   double *pinv;     // PB  1 / L[piv][step]
   double *Lpp;      // PB x PB  L rows of the panel's pivots (panel columns)
@@ -568,7 +568,25 @@ __global__ __launch_bounds__(256) void piv_panel_kernel(int n, int k, int ps, in
 // operation sequence (explicit fma), so candidates and the rest agree bit
 // for bit.  Selection: two 11-bit radix passes on the diagonal's bit pattern
 // (positive doubles order like their bits), set = rows strictly above the
-// crossing bin (|set| <= SEL).
+// crossing bin (|set| <= the level's count).
+// Levels.  The tau rule gives dgeqp3's choice at any candidate count; the
+// count only trades the cost of a step against the length of a panel.  A
+// panel runs at one of three levels: 256 or 512 candidates on four waves (one
+// per SIMD; one or two candidates per thread), or 1024 on all eight.  The
+// selection always uses the eight waves; below 1024 the upper four leave
+// before the steps.  The level is a word of sstate, set by each panel for
+// the next (lev_pays, LEV_DOWN at sel_steps' end); TG_PIV_LEVEL forces it.
+// Every level runs the same operations on a candidate's lr, dc, ljj and inv,
+// so piv_fill_kernel reproduces them bit for bit whatever the level.
+// Measured at n = 4096, k = 3058 (profiles/piv/README.md): waves of the
+// eight-wave form wait 53% of their cycles and issue 32% (VALU 43% of a
+// SIMD's cycles), instruction-cache misses are 0.1% of fetches; a step is
+// 1.9 us at 1024 candidates, about 1.5 us at 512 and 1.4 us at 256: three
+// quarters of it is a latency chain that fewer lanes do not shorten.  256
+// candidates give panels of 22 steps on average there, which costs more in
+// extra panels than the shorter steps save, so the adaptive rule spends most
+// panels at 512.  Only reasoned: how the waits split into barrier, LDS and
+// gather.
 // The candidate-set path keeps H_k compacted: at a panel starting at step ps
 // the Schur complement of the unpivoted rows is the leading (n - ps)^2 block,
 // row / column x holding the row at position ps + x (leading dimension n).
@@ -601,15 +619,59 @@ __device__ __forceinline__ size_t hk_at(int a, int b, int n) {
   return size_t(max(a, b)) * n + min(a, b);
 }
 
+// n <= 32768 on this path (compact_pivot), so an entry's index fits 32 bits
+__device__ __forceinline__ unsigned hk_at32(int a, int b, int n) {
+  return unsigned(max(a, b)) * unsigned(n) + unsigned(min(a, b));
+}
+
 constexpr int STH = 512;        // threads of piv_sel_kernel (8 waves)
-constexpr int CPT = SEL / STH;  // candidates per thread
+
+// Candidate levels: 256 (four waves, one candidate per thread), 512 (four
+// waves, two per thread), 1024 (eight waves, two per thread).  The words of
+// sstate behind the two step counts hold the adaptive level and the counts
+// TG_PIV_STATS prints; piv_init2_kernel zeroes them, so a solve starts at the
+// lowest level (that can pay at its size, lev_pays).
+constexpr int NLEV = 3;
+constexpr int LEV_DOWN = 8;  // panels at a level before the next one tries the level below
+enum { SS_LEV = 2, SS_RUN = 3, SS_PANELS = 4, SS_EARLY = 5, SS_ESC = 6, SS_NLEV = 7, SS_NEED = 10 };
+static_assert(SS_NLEV + NLEV <= SS_NEED && SS_NEED + NLEV - 1 <= 16, "sstate words");
+
+// Does a narrower level pay for a panel of `rem` unpivoted rows that loses
+// `lost` of its PB steps to the tau rule?  The lost steps cost their share of
+// one more panel (selection and fill, about 35 us, plus the Schur update,
+// about 19 us at the flagship's mean rem^2 = 0.44 * 4096^2, i.e. (rem / 64)^2
+// / 94 us); four waves save about 0.45 us a step, 14 us a full panel
+// (measured at n = 4096, profiles/piv/README.md).  lost = 1 asks whether the
+// level can pay at all at this size.
+__device__ __forceinline__ bool lev_pays(int rem, int lost) {
+  const int r = rem >> 6, extra_us = 35 + r * r / 94, gain_us = 14;
+  return lost * extra_us < PB * gain_us;
+}
+
+// What the selection hands to a panel's steps.
+struct SelPanel {
+  int n, k, ps, pe, nset, bp, brow, bo, lev;
+  bool adaptive;
+  double tau, bv;
+  const double *dS;
+  const int32_t *pS;
+  int *permL;
+  const int *cand;
+  double2 *rec;
+  int *reco;
+  double *lrow;
+  unsigned long long t0;  // TG_SEL_PHASES: the last time stamp
+};
+template <int MODE, int NW, int CP>
+__device__ __forceinline__ void sel_steps(const SelPanel &sp, PivWs w,
+                                          const double *__restrict__ Hc);
 
 // Block argmax of (v desc, p asc) carrying a row id r (positions are
 // unique).  Wave stage: the maximum of v alone through six exchange stages
 // (v_permlane{32,16}_swap pairs, DPP row mirrors / quad perms) with v_max_f64,
 // then the holder found by a ballot; only a tie on v (rare: exhausted
 // candidates at -inf) takes the slower min-position pass.  One barrier; the
-// eight wave records are merged by every thread with selects.
+// NW wave records are merged by every thread with selects.
 // v_max_f64 without the operand canonicalisation fmax() adds for values that
 // come out of lane exchanges
 __device__ inline double vmax_d(double a, double b) {
@@ -645,6 +707,7 @@ template <int S>
 __device__ inline int wave_min_stage(int x) {
   return min(x, partner<S>(x));
 }
+template <int NW>
 __device__ inline void block_argmax_sel(double &v, int &p, int &r, int &o, double2 *rec,
                                         int *reco) {
   const double m = wave_max_d(v);
@@ -671,17 +734,17 @@ __device__ inline void block_argmax_sel(double &v, int &p, int &r, int &o, doubl
     reco[threadIdx.x >> 6] = wo;
   }
   __syncthreads();
-  double2 x[STH / 64];
+  double2 x[NW];
 #pragma unroll
-  for (int q = 0; q < STH / 64; ++q) x[q] = rec[q];
+  for (int q = 0; q < NW; ++q) x[q] = rec[q];
   v = x[0].x;
 #pragma unroll
-  for (int q = 1; q < STH / 64; ++q) v = vmax_d(v, x[q].x);
+  for (int q = 1; q < NW; ++q) v = vmax_d(v, x[q].x);
   p = INT_MAX;
   r = 0;
   o = 0;
 #pragma unroll
-  for (int q = 0; q < STH / 64; ++q) {
+  for (int q = 0; q < NW; ++q) {
     const int op = __double2hiint(x[q].y);
     const bool take = (x[q].x == v) & (op < p);
     p = take ? op : p;
@@ -762,7 +825,7 @@ static_assert((1 << CC_TAG) > SEL, "slot field");
 
 template <int MODE>
 __global__ __launch_bounds__(STH) void piv_sel_kernel(int n, int k, PivWs w,
-                                                      const double *__restrict__ Hc) {
+                                                      const double *__restrict__ Hc, int flev) {
   extern __shared__ int permL[];  // n: position -> row
   __shared__ unsigned hist[HPAD];
   __shared__ int cand[SEL + 1];  // + trash slot for branch-free compaction
@@ -779,6 +842,15 @@ __global__ __launch_bounds__(STH) void piv_sel_kernel(int n, int k, PivWs w,
     return;
   }
   const int pe = min(ps + PB, k);
+  // this panel's level and its candidate count: flev >= 0 forces the level;
+  // the candidate-block modes keep the widest, and so does a panel whose
+  // Schur update is so large that losing a single step costs more than four
+  // waves save
+  const int lev = MODE != SEL_FULL       ? NLEV - 1
+                  : flev >= 0            ? flev
+                  : !lev_pays(n - ps, 1) ? NLEV - 1
+                                         : min(max(w.sstate[SS_LEV], 0), NLEV - 1);
+  const int nsel = SEL >> (NLEV - 1 - lev);
 #ifdef TG_SEL_PHASES
   uint64_t selt_last = 0;
 #endif
@@ -865,8 +937,8 @@ __global__ __launch_bounds__(STH) void piv_sel_kernel(int n, int k, PivWs w,
 #pragma unroll
   for (int q = 0; q < STH / 64; ++q) valid += scnt[q];
   SELT(10)
-  if (valid > SEL) {  // uniform
-    if (wid == 0) hist_scan(hist, SEL, sel);  // sel[0] = b1, sel[1] = count above
+  if (valid > nsel) {  // uniform
+    if (wid == 0) hist_scan(hist, nsel, sel);  // sel[0] = b1, sel[1] = count above
     __syncthreads();
     for (int x = tid; x < HPAD; x += STH) hist[x] = 0u;
     __syncthreads();
@@ -888,7 +960,7 @@ __global__ __launch_bounds__(STH) void piv_sel_kernel(int n, int k, PivWs w,
       }
     }
     __syncthreads();
-    if (wid == 0) hist_scan(hist, SEL - sel[1], sel + 2);
+    if (wid == 0) hist_scan(hist, nsel - sel[1], sel + 2);
     __syncthreads();
   }
   SELT(11)
@@ -962,7 +1034,7 @@ __global__ __launch_bounds__(STH) void piv_sel_kernel(int n, int k, PivWs w,
 #pragma unroll
   for (int q = 0; q < STH / 64; ++q) nset += scnt[q];
   bo = bp - ps;  // compact index of the step-0 pivot (positions unchanged so far)
-  block_argmax_sel(bv, bp, brow, bo, rec, reco);
+  block_argmax_sel<STH / 64>(bv, bp, brow, bo, rec, reco);
   if constexpr (MODE == SEL_SELECT) {
     for (int c = tid; c < nset; c += STH) {
       w.cand[c] = cand[c];
@@ -981,13 +1053,62 @@ __global__ __launch_bounds__(STH) void piv_sel_kernel(int n, int k, PivWs w,
     return;
   }
   }  // MODE != SEL_STEPS
-  int rc[CPT], posc[CPT], oc[CPT];
-  double dc[CPT];
-  bool done[CPT];
-  double lr[CPT][PB];
+  SelPanel sp{n,   k,  ps, pe,    nset, bp,   brow, bo,   lev,  flev < 0 && MODE == SEL_FULL,
+              tau, bv, dS, pS,    permL, cand, rec,  reco, lrow,
+#ifdef TG_SEL_PHASES
+              selt_last
+#else
+              0
+#endif
+  };
+  if constexpr (MODE != SEL_FULL) {
+    sel_steps<MODE, STH / 64, 2>(sp, w, Hc);
+  } else {
+    if (lev == NLEV - 1) {  // uniform
+      sel_steps<MODE, STH / 64, 2>(sp, w, Hc);
+      return;
+    }
+    // one wave per SIMD from here on: the other four leave (a workgroup
+    // barrier counts the waves that have not ended)
+    if (wid >= 4) return;
+    if (lev == 1) sel_steps<MODE, 4, 2>(sp, w, Hc);
+    else sel_steps<MODE, 4, 1>(sp, w, Hc);
+  }
+}
+
+// The panel's steps on NW waves holding CP candidates per thread (NW * 64 * CP
+// >= the level's candidate count), then the panel's bookkeeping: positions,
+// compact indices, step counts and the next panel's level.
+template <int MODE, int NW, int CP>
+__device__ __forceinline__ void sel_steps(const SelPanel &sp, PivWs w,
+                                          const double *__restrict__ Hc) {
+  constexpr int NT = NW * 64;
+  const int tid = threadIdx.x;
+  const int n = sp.n, k = sp.k, ps = sp.ps, pe = sp.pe, nset = sp.nset;
+  const double tau = sp.tau;
+  const double *dS = sp.dS;
+  const int32_t *pS = sp.pS;
+  int *permL = sp.permL;
+  const int *cand = sp.cand;
+  double2 *rec = sp.rec;
+  int *reco = sp.reco;
+  double *lrow = sp.lrow;
+#ifdef TG_SEL_PHASES
+  uint64_t selt_last = sp.t0;
+#endif
+  // the level's run length and the counts, read here so that the panel's end
+  // only stores
+  const int ss_run = w.sstate[SS_RUN], ss_esc = w.sstate[SS_ESC], ss_panels = w.sstate[SS_PANELS],
+            ss_early = w.sstate[SS_EARLY], ss_nlev = w.sstate[SS_NLEV + sp.lev],
+            ss_need_up = w.sstate[SS_NEED + min(sp.lev, NLEV - 2)],      // leaving this level upwards
+            ss_need_dn = w.sstate[SS_NEED + max(sp.lev - 1, 0)];         // entering the level below
+  int rc[CP], posc[CP], oc[CP];
+  double dc[CP];
+  bool done[CP];
+  double lr[CP][PB];
 #pragma unroll
-  for (int u = 0; u < CPT; ++u) {
-    const int c = tid + u * STH;
+  for (int u = 0; u < CP; ++u) {
+    const int c = tid + u * NT;
     rc[u] = c < nset ? cand[c] : -1;
     posc[u] = rc[u] >= 0 ? pS[rc[u]] : n;
     oc[u] = rc[u] >= 0 ? posc[u] - ps : 0;  // compact index in this panel's H_k
@@ -996,9 +1117,9 @@ __global__ __launch_bounds__(STH) void piv_sel_kernel(int n, int k, PivWs w,
 #pragma unroll
     for (int l = 0; l < PB; ++l) lr[u][l] = 0.0;
   }
-  int piv = brow, q = bp, opiv = bo;
+  int piv = sp.brow, q = sp.bp, opiv = sp.bo;
   int cpiv = -1;  // SEL_STEPS: the pivot's candidate slot (step 0: from H_k)
-  double dpiv = bv;
+  double dpiv = sp.bv;
   int tdone = 0;
   SELT(1)
   // steps unrolled: the panel column t is a compile-time register index
@@ -1012,16 +1133,16 @@ __global__ __launch_bounds__(STH) void piv_sel_kernel(int n, int k, PivWs w,
       double v = -INFINITY;
       int p = n, r = -1, o = 0;
 #pragma unroll
-      for (int u = 0; u < CPT; ++u) {
+      for (int u = 0; u < CP; ++u) {
         const bool take = !done[u] & ((dc[u] > v) | ((dc[u] == v) & (posc[u] < p)));
         v = take ? dc[u] : v;
         p = take ? posc[u] : p;
         r = take ? rc[u] : r;
         // SEL_STEPS: the candidate slot rides along above the compact index
-        o = take ? (MODE == SEL_STEPS ? oc[u] | ((tid + u * STH + 1) << 16) : oc[u]) : o;
+        o = take ? (MODE == SEL_STEPS ? oc[u] | ((tid + u * NT + 1) << 16) : oc[u]) : o;
       }
       SELT(4)
-      block_argmax_sel(v, p, r, o, rec, reco);
+      block_argmax_sel<NW>(v, p, r, o, rec, reco);
       SELT(5)
       active = v > tau;
       if (!active) return;
@@ -1031,18 +1152,18 @@ __global__ __launch_bounds__(STH) void piv_sel_kernel(int n, int k, PivWs w,
       opiv = MODE == SEL_STEPS ? (o & 0xffff) : o;
       cpiv = MODE == SEL_STEPS ? (o >> 16) - 1 : -1;
     }
-    double hv[CPT];
+    double hv[CP];
     if (MODE == SEL_STEPS && cpiv >= 0) {  // uniform: the pivot's candidate row of Cc
       const double *crow = w.Cc + size_t(cpiv) * SEL;
 #pragma unroll
-      for (int u = 0; u < CPT; ++u) hv[u] = crow[tid + u * STH];
+      for (int u = 0; u < CP; ++u) hv[u] = crow[tid + u * NT];
     } else {
 #pragma unroll
-      for (int u = 0; u < CPT; ++u)  // H_k[piv][candidate], issued before the hand-off
-        hv[u] = Hc[hk_at(opiv, oc[u], n)];  // unconditional; masked below
+      for (int u = 0; u < CP; ++u)  // H_k[piv][candidate], issued before the hand-off
+        hv[u] = Hc[hk_at32(opiv, oc[u], n)];  // unconditional; masked below
     }
 #pragma unroll
-    for (int u = 0; u < CPT; ++u)
+    for (int u = 0; u < CP; ++u)
       if (rc[u] == piv) {
 #pragma unroll
         for (int l = 0; l < t; ++l) lrow[l] = lr[u][l];
@@ -1068,7 +1189,7 @@ __global__ __launch_bounds__(STH) void piv_sel_kernel(int n, int k, PivWs w,
 #pragma unroll
     for (int l = 0; l < t; ++l) lrw[l] = lrow[l];
 #pragma unroll
-    for (int u = 0; u < CPT; ++u) {  // branch-free: every slot computes, selects keep
+    for (int u = 0; u < CP; ++u) {  // branch-free: every slot computes, selects keep
       const bool isp = rc[u] == piv;  // the pivot: dgeqp3 swap of positions i and q
       const bool upd = !done[u] & !isp;
       double v = hv[u];
@@ -1093,9 +1214,9 @@ __global__ __launch_bounds__(STH) void piv_sel_kernel(int n, int k, PivWs w,
   __syncthreads();
   // compact index (in this panel's H_k) of the row now at position x >= ps:
   // read from the panel-start positions before they are overwritten
-  for (int x = ps + tid; x < n; x += STH) w.oidx[x - ps] = pS[permL[x]] - ps;
+  for (int x = ps + tid; x < n; x += NT) w.oidx[x - ps] = pS[permL[x]] - ps;
   __syncthreads();
-  for (int x = tid; x < n; x += STH) {
+  for (int x = tid; x < n; x += NT) {
     const int r = permL[x];
     w.perm[x] = r;
     w.pos[r] = x;
@@ -1103,6 +1224,32 @@ __global__ __launch_bounds__(STH) void piv_sel_kernel(int n, int k, PivWs w,
   if (tid == 0) {
     w.sstate[0] = ps + tdone;
     w.sstate[1] = tdone;
+    // ended by the tau rule: the candidates ran out against the bound of the rest
+    const bool early = tdone < PB && ps + tdone < k;
+    if (sp.adaptive) {
+      // up at once when the tau rule cuts a panel short by more than the
+      // narrower level saves (lev_pays: an end one or two steps early costs
+      // less than the wider level's steps unless the Schur update is large),
+      // down one after `need` panels in a row without such an end.  need
+      // starts at LEV_DOWN and doubles, for the rest of the solve, with every
+      // raise out of the level below, so a level that keeps failing is
+      // retried ever more rarely.
+      const bool shorted = early && !lev_pays(n - ps, pe - ps - tdone);
+      int lev = sp.lev, run = shorted ? 0 : ss_run + 1;
+      if (shorted && lev < NLEV - 1) {
+        w.sstate[SS_NEED + lev] = min(2 * max(ss_need_up, LEV_DOWN), 1 << 20);
+        ++lev;
+        w.sstate[SS_ESC] = ss_esc + 1;
+      } else if (lev > 0 && run >= max(ss_need_dn, LEV_DOWN)) {
+        --lev;
+        run = 0;
+      }
+      w.sstate[SS_LEV] = lev;
+      w.sstate[SS_RUN] = run;
+    }
+    w.sstate[SS_PANELS] = ss_panels + 1;
+    w.sstate[SS_EARLY] = ss_early + early;
+    w.sstate[SS_NLEV + sp.lev] = ss_nlev + 1;
   }
 }
 
@@ -2251,6 +2398,13 @@ static int pivot_core_sel(hipStream_t st, PivWs &w, int n, int k) {
     return e;
   };
   if (ccb) TG_HIP(hipMemsetAsync(w.cidx, 0xff, sizeof(int32_t) * size_t(n), st));  // no tags
+  // TG_PIV_LEVEL=256|512|1024 forces the candidate level of every panel
+  // (development switch, per call); unset: chosen on the device, panel by panel
+  int flev = -1;
+  if (const char *pl = getenv("TG_PIV_LEVEL")) {
+    const int v = atoi(pl);
+    flev = v == 256 ? 0 : v == 512 ? 1 : v == 1024 ? 2 : -1;
+  }
   int done = 0;
   // a panel's Schur update runs at the head of the next panel: with the
   // candidate block, between that panel's selection and its steps
@@ -2266,7 +2420,8 @@ static int pivot_core_sel(hipStream_t st, PivWs &w, int n, int k) {
       const int rows = n - (done + p);
       if (ccb && pend_rows > 0) {
         auto tk = tg::prof_begin(st, tg::PROF_PIVSTEP, 8.0 * double(n) * 2, 0.0);
-        hipLaunchKernelGGL(piv_sel_kernel<SEL_SELECT>, dim3(1), dim3(STH), lds, st, n, k, w, hc);
+        hipLaunchKernelGGL(piv_sel_kernel<SEL_SELECT>, dim3(1), dim3(STH), lds, st, n, k, w, hc,
+                           NLEV - 1);
         tg::prof_end(st, tk);
         TG_LAUNCHED();
         TG_HIP(schur_compact(pend_rows, 1));
@@ -2275,9 +2430,11 @@ static int pivot_core_sel(hipStream_t st, PivWs &w, int n, int k) {
       }
       auto tok = tg::prof_begin(st, tg::PROF_PIVSTEP, 8.0 * double(n) * PB * 3, 0.0);
       if (ccb && pend_rows > 0)
-        hipLaunchKernelGGL(piv_sel_kernel<SEL_STEPS>, dim3(1), dim3(STH), lds, st, n, k, w, hc);
+        hipLaunchKernelGGL(piv_sel_kernel<SEL_STEPS>, dim3(1), dim3(STH), lds, st, n, k, w, hc,
+                           NLEV - 1);
       else
-        hipLaunchKernelGGL(piv_sel_kernel<SEL_FULL>, dim3(1), dim3(STH), lds, st, n, k, w, hc);
+        hipLaunchKernelGGL(piv_sel_kernel<SEL_FULL>, dim3(1), dim3(STH), lds, st, n, k, w, hc,
+                           flev);
       // one wave per workgroup: the gathers of the pivots' columns spread
       // over 4x the CUs of 256-thread groups (n = 12,288: -1.4 ms per solve)
       hipLaunchKernelGGL(piv_fill_kernel<64>, dim3(tg::cdiv(rows, 64)), dim3(64), 0, st, n, k, w, hc);
@@ -2291,6 +2448,16 @@ static int pivot_core_sel(hipStream_t st, PivWs &w, int n, int k) {
     if (h >= k) break;
     pend_rows = n - (done + P - 1);  // the round's last panel, updated at the next one's head
     done = h;
+  }
+  // TG_PIV_STATS=1: one line per call (development switch)
+  if (const char *pst = getenv("TG_PIV_STATS"); pst && pst[0] == '1') {
+    int32_t h[16];
+    TG_HIP(hipMemcpyAsync(h, w.sstate, sizeof(h), hipMemcpyDeviceToHost, st));
+    TG_HIP(hipStreamSynchronize(st));
+    fprintf(stderr,
+            "pivot stats: n=%d k=%d panels=%d early=%d escalations=%d level256=%d level512=%d "
+            "level1024=%d\n",
+            n, k, h[SS_PANELS], h[SS_EARLY], h[SS_ESC], h[SS_NLEV], h[SS_NLEV + 1], h[SS_NLEV + 2]);
   }
   return 0;
 }
