@@ -1,5 +1,5 @@
 // Blocked Householder QR, R only, FP64, for gfx950 (tg_qr_r and the fallback of
-// the U factors in factor.hip; the reference's QR is gptq_utils.py:120).
+// the U factors in ufactor.hip; the reference's QR is gptq_utils.py:120).
 //
 // Communication-avoiding (TSQR-tree) form: no launch waits on another
 // workgroup.  For each panel of HB = 32 columns starting at j0 (m = k - j0

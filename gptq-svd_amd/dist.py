@@ -131,7 +131,7 @@ class UrxHip:
 
     def small_m(self, k: int, m: int) -> bool:
         import os
-        e = os.environ.get("TG_URX_SMALLM")  # the library's switch (factor.hip urx_small_m)
+        e = os.environ.get("TG_URX_SMALLM")  # the library's switch (ufactor.hip urx_small_m)
         return e == "1" if e is not None else m * 16 <= k
 
     def _ws(self, n, k, dev):

@@ -7,7 +7,7 @@ The per-process pieces run as a numpy stand-in of the library's explicit form
 Cholesky of J N J, U11 = V^-1, U12 = U11 C): the gathered U of every world
 size equals the one-process U bit for bit, and U is the R factor of
 QR(S^-1 R_x), S = R_x R_x^T (gptq_utils.py:118-124 through the identity in
-csrc/factor.hip), to 1e-8.  The HIP pieces' column independence is
+csrc/ufactor.hip), to 1e-8.  The HIP pieces' column independence is
 tests/test_gpu_urx_sharded.py."""
 import os
 import socket

@@ -2,7 +2,7 @@
 
 Both U paths form U from the Cholesky factor of a Gram matrix, which squares
 the condition number relative to the reference's Householder QR
-(gptq_utils.py:120).  The library guards it (factor.hip, "Conditioning
+(gptq_utils.py:120).  The library guards it (ufactor.hip, "Conditioning
 guard"): a breakdown or a large diagonal range of the first factor triggers
 CholeskyQR refinement (shifted CholeskyQR3 after a breakdown); a factor that
 still breaks down raises RuntimeError instead of returning NaN.

@@ -65,8 +65,6 @@ def rel(a, b):
     {"TG_XM_KSPLIT": "3"},
     {"TG_URX_SMALLM": "1"},
     {"TG_URX_INV": "1"},
-    {"TG_SCHUR_MIRROR": "1"},
-    {"TG_PIV_CC": "1"},
     {"TG_BT_Q2_LDS": "0"},
     {"TG_BT_Q1_LDS": "0"},
     {"TG_BT_TF_SIDE": "0"},

@@ -1,4 +1,4 @@
-"""Householder QR fallback of the U factors (factor.hip + hqr.hip, TG_U_QR).
+"""Householder QR fallback of the U factors (ufactor.hip + hqr.hip, TG_U_QR).
 
 tg_u_factor / tg_u_factor_rx / tg_urx_u11 take U from the Cholesky factor of a
 Gram matrix, which squares the condition number; past cond(A[:, :k]) ~ 3e13

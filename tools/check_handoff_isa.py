@@ -66,9 +66,9 @@ KERNELS = {
     # arguments (rule A still covers every signal, the out-of-line fallback's too)
     "pqr.o": [("pqr_kernel", False, False, False), ("ph_householder", False, False, False)],
     "band.o": [("xm_kernelILi1E", False, False, True), ("xm_kernelILi2E", False, False, True)],
-    "factor.o": [("piv_panel_kernelILi1E", False, False, True),
-                 ("piv_panel_kernelILi2E", False, False, True),
-                 ("piv_step_kernel", False, False, True)],
+    "pivot.o": [("piv_panel_kernelILi1E", False, False, True),
+                ("piv_panel_kernelILi2E", False, False, True),
+                ("piv_step_kernel", False, False, True)],
 }
 STORE = re.compile(r"^(global_store|buffer_store|global_atomic|flat_store|flat_atomic)")
 EXEMPT = ("global_atomic_or", "global_atomic_swap")  # stall marks, resets, records

@@ -1,5 +1,5 @@
 """A/B of environment switches on the factorisation time (development tool):
-    N=4096 REPS=8 python tools/env_ab.py TG_SCHUR_MIRROR=0 TG_SCHUR_MIRROR=1
+    N=4096 REPS=8 python tools/env_ab.py TG_SYR2K_PERSIST=1 TG_SYR2K_PERSIST=0
 Each variant runs process_hessian_alt on the same synthetic H (3n/4 fp16
 rows; ROWS=2 for full rank) in one process, variants interleaved rep by rep;
 prints the median and min factor ms per variant."""
