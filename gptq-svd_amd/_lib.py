@@ -94,6 +94,10 @@ _SIGS = {
     "tg_dequant_mx": ([_vp, _vp, _vp, _i, _i, _i, _vp, _i, _i64], _i),
     "tg_qgemm_mx": ([_vp, _vp, _i, _i, _i64, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _i64, _vp,
                      _sz], _i),
+    "tg_quant_act_mx": ([_vp, _vp, _i, _i, _i64, _i, _i, _vp, _i64, _vp], _i),
+    "tg_qgemm_mx_act_workspace_size": ([_i, _i, _i], _sz),
+    "tg_qgemm_mx_act": ([_vp, _vp, _i, _i, _i64, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _i64,
+                         _vp, _sz], _i),
 }
 
 EXPORTED = []
@@ -108,6 +112,8 @@ for _name, (_args, _res) in _SIGS.items():
 TG_F16, TG_BF16, TG_F32, TG_F64 = 0, 1, 2, 3
 TG_FMT_MXFP4 = 1
 WEIGHT_FORMATS = {"mxfp4": TG_FMT_MXFP4}    # tg_weight_format; "int" is the uniform integer grid
+TG_ACT_MXFP8 = 1
+ACT_FORMATS = {"mxfp8": TG_ACT_MXFP8}       # tg_act_format; None keeps the 16-bit activations
 RULES = {"none": 0, "energy": 1, "mean_trimmed": 2}
 DTYPES = {torch.float16: TG_F16, torch.bfloat16: TG_BF16, torch.float32: TG_F32,
           torch.float64: TG_F64}

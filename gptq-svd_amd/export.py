@@ -118,7 +118,8 @@ def _set_submodule(model: torch.nn.Module, name: str, new: torch.nn.Module) -> N
     setattr(parent, leaf, new)
 
 
-def load_quantized(model: torch.nn.Module, path: str, device=None) -> torch.nn.Module:
+def load_quantized(model: torch.nn.Module, path: str, device=None,
+                   act_format=None) -> torch.nn.Module:
     """Load a checkpoint written by save_quantized into `model` (the dense
     architecture, any weights) and return it: every ``nn.Linear`` whose
     ``<name>.qweight`` is in the checkpoint becomes a ``qlinear.QuantLinear``
@@ -126,12 +127,23 @@ def load_quantized(model: torch.nn.Module, path: str, device=None) -> torch.nn.M
     tensor is loaded as is.  ``quantize_config.json`` must be a static-group
     ``desc_act=false`` configuration with supported bits, and every ``g_idx``
     must be the trivial ``arange(in) // group`` map (act-order checkpoints are
-    out of scope).  `device`: where the model is moved (default: it stays)."""
-    from .qlinear import QuantLinear
+    out of scope).  `device`: where the model is moved (default: it stays).
+    `act_format`: a run-time choice for MXFP4 checkpoints, handed to every
+    ``MXQuantLinear`` (None: 16-bit activations; "mxfp8": the block-scaled W4A8
+    kernel); with an integer checkpoint it is an error.  The checkpoint does not
+    record it."""
+    from .qlinear import QuantLinear, _check_act_format
+    _check_act_format(act_format)
+    if act_format is not None:                   # before any tensor is read
+        with open(os.path.join(path, "quantize_config.json")) as f:
+            fmt = json.load(f).get("checkpoint_format", "gptq_v2")
+        if fmt != "mxfp4":
+            raise ValueError(f"act_format={act_format!r} needs an mxfp4 checkpoint; this one is "
+                             f"{fmt!r}")
     tensors, qc = read_quantized(path)
     bits, group = int(qc["bits"]), int(qc["group_size"])
     if qc.get("checkpoint_format") == "mxfp4":
-        return _load_mx(model, tensors, qc, device)
+        return _load_mx(model, tensors, qc, device, act_format)
     if bits not in (2, 3, 4, 8):
         raise ValueError(f"quantize_config.json: bits={bits} is not one of 2, 3, 4, 8")
     if qc.get("desc_act", False):
@@ -176,7 +188,7 @@ def load_quantized(model: torch.nn.Module, path: str, device=None) -> torch.nn.M
 
 
 def _load_mx(model: torch.nn.Module, tensors: Dict[str, torch.Tensor], qc: Dict[str, Any],
-             device) -> torch.nn.Module:
+             device, act_format=None) -> torch.nn.Module:
     """load_quantized for ``checkpoint_format: "mxfp4"``: every ``nn.Linear``
     with a ``<name>.qweight`` becomes a ``qlinear.MXQuantLinear``."""
     from .qlinear import MXQuantLinear
@@ -204,7 +216,8 @@ def _load_mx(model: torch.nn.Module, tensors: Dict[str, torch.Tensor], qc: Dict[
             bias = bias.to(lin.bias.dtype)
         try:
             q = MXQuantLinear.from_packed(tensors[keys["qweight"]], tensors[keys["scales"]],
-                                          bias=bias, device=lin.weight.device)
+                                          bias=bias, device=lin.weight.device,
+                                          act_format=act_format)
         except ValueError as e:
             raise ValueError(f"{name}: {e}") from None
         if (q.out_features, q.in_features) != (lin.out_features, lin.in_features):

@@ -18,6 +18,11 @@ MXFP4 checkpoints (``checkpoint_format: "mxfp4"``) hold ``qweight`` int32
 and no ``g_idx``.  w = +-{0, .5, 1, 1.5, 2, 3, 4, 6}[code & 7] * 2^(byte - 127).
 ``dequantize_packed_mx`` and ``MXQuantLinear`` are their consumers
 (``tg_dequant_mx``, ``tg_qgemm_mx``).
+
+MXFP8 activations (A16, opt-in): ``MXQuantLinear(..., act_format="mxfp8")``
+quantises x to e4m3 with one E8M0 byte per 32 columns (``quantize_act_mx``,
+``tg_quant_act_mx``) and multiplies on the block-scaled MFMA instruction
+(``tg_qgemm_mx_act``): W4A8, different numerics from the weights-only path.
 """
 from __future__ import annotations
 
@@ -26,9 +31,11 @@ from typing import Optional
 import torch
 from torch import nn
 
-from ._lib import DTYPES, TG_FMT_MXFP4, call, lib, ptr, require_cuda, stream, workspace
+from ._lib import (ACT_FORMATS, DTYPES, TG_FMT_MXFP4, call, lib, ptr, require_cuda, stream,
+                   workspace)
 
-__all__ = ["QuantLinear", "dequantize_packed", "MXQuantLinear", "dequantize_packed_mx"]
+__all__ = ["QuantLinear", "dequantize_packed", "MXQuantLinear", "dequantize_packed_mx",
+           "quantize_act_mx", "dequantize_act_mx"]
 
 _BITS = (2, 3, 4, 8)
 
@@ -212,17 +219,64 @@ def dequantize_packed_mx(qweight: torch.Tensor, scales: torch.Tensor,
     return out
 
 
+def _check_act_format(act_format) -> None:
+    if act_format is not None and (not isinstance(act_format, str)
+                                   or act_format not in ACT_FORMATS):
+        raise ValueError(f"act_format must be None or one of {sorted(ACT_FORMATS)}, got "
+                         f"{act_format!r}")
+
+
+def quantize_act_mx(x: torch.Tensor):
+    """MXFP8 image of fp16 / bf16 activations (..., n), n % 32 == 0:
+    ``(xq uint8 (..., n), xs uint8 (..., n/32))``, e4m3fn bytes (OCP) and the
+    E8M0 byte of each block of 32 columns (``tg_quant_act_mx``)."""
+    require_cuda(x, "quantize_act_mx input")
+    if x.dtype not in (torch.float16, torch.bfloat16):
+        raise RuntimeError(f"quantize_act_mx takes float16 or bfloat16, got {x.dtype}")
+    n = x.shape[-1]
+    if n == 0 or n % 32:
+        raise ValueError(f"quantize_act_mx needs a last dim that is a multiple of 32, got {n}")
+    x2 = x.reshape(-1, n)
+    T = x2.shape[0]
+    xq = torch.empty((T, n), dtype=torch.uint8, device=x.device)
+    xs = torch.empty((T, n // 32), dtype=torch.uint8, device=x.device)
+    if T > 0:
+        if x2.stride(1) != 1 or (T > 1 and x2.stride(0) < n):
+            x2 = x2.contiguous()
+        ldx = x2.stride(0) if T > 1 else n
+        with torch.cuda.device(x.device):
+            call("tg_quant_act_mx", stream(), ptr(x2), DTYPES[x.dtype], T, ldx, n,
+                 ACT_FORMATS["mxfp8"], ptr(xq), n, ptr(xs))
+    return xq.reshape(*x.shape[:-1], n), xs.reshape(*x.shape[:-1], n // 32)
+
+
+def dequantize_act_mx(xq: torch.Tensor, xs: torch.Tensor,
+                      dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """``float(e4m3(xq)) * 2^(xs - 127)`` rounded once to `dtype` (plain torch;
+    exact in fp32, and in bf16 for every block scale bf16 can hold)."""
+    v = xq.view(torch.float8_e4m3fn).to(torch.float32)
+    e = xs.to(torch.int32)
+    # 2^(byte - 127) built in the exponent field; byte 0 is the subnormal 2^-127
+    s = torch.where(e > 0, e << 23, torch.full_like(e, 0x00400000)).view(torch.float32)
+    return (v * s.repeat_interleave(32, dim=-1)).to(dtype)
+
+
 class MXQuantLinear(nn.Module):
     """A linear layer whose weight stays packed as MXFP4: buffers ``qweight``
     int32 (in/8, out) and ``scales`` uint8 (in/32, out), the checkpoint's keys.
-    Weights only: activations are fp16 / bf16 and the decoded weight feeds the
-    16-bit kernels of ``QuantLinear`` (``tg_qgemm_mx``)."""
+    ``act_format=None``: weights only, activations are fp16 / bf16 and the
+    decoded weight feeds the 16-bit kernels of ``QuantLinear`` (``tg_qgemm_mx``).
+    ``act_format="mxfp8"``: the activations are quantised to MXFP8 per call and
+    both operands feed the block-scaled MFMA (``tg_qgemm_mx_act``); a run-time
+    choice that the checkpoint does not record."""
 
     w_bits, group_size = 4, 32
 
     def __init__(self, in_features: int, out_features: int, bias: bool = False,
-                 bias_dtype: torch.dtype = torch.float16, device=None):
+                 bias_dtype: torch.dtype = torch.float16, device=None, act_format=None):
         super().__init__()
+        _check_act_format(act_format)
+        self.act_format = act_format
         if in_features % 32 or (out_features * 4) % 32:
             raise ValueError(f"MXQuantLinear needs in_features % 32 == 0 and out_features % 8 == 0 "
                              f"(got in={in_features}, out={out_features})")
@@ -239,12 +293,14 @@ class MXQuantLinear(nn.Module):
 
     @classmethod
     def from_packed(cls, qweight: torch.Tensor, scales: torch.Tensor,
-                    bias: Optional[torch.Tensor] = None, device=None) -> "MXQuantLinear":
+                    bias: Optional[torch.Tensor] = None, device=None,
+                    act_format=None) -> "MXQuantLinear":
         """From the packed pair (a checkpoint's, or ``pack_quantized``'s)."""
         m, n = _shapes_mx(qweight, scales)
         dev = device if device is not None else qweight.device
         q = cls(n, m, bias=bias is not None,
-                bias_dtype=bias.dtype if bias is not None else torch.float16, device=dev)
+                bias_dtype=bias.dtype if bias is not None else torch.float16, device=dev,
+                act_format=act_format)
         q.qweight.copy_(qweight)
         q.scales.copy_(scales)
         if bias is not None:
@@ -253,7 +309,7 @@ class MXQuantLinear(nn.Module):
 
     def extra_repr(self) -> str:
         return (f"in_features={self.in_features}, out_features={self.out_features}, "
-                f"format=mxfp4, bias={self.bias is not None}")
+                f"format=mxfp4, bias={self.bias is not None}, act_format={self.act_format}")
 
     def dequantize(self, dtype: torch.dtype = torch.float16) -> torch.Tensor:
         """The dense (out, in) weight."""
@@ -278,6 +334,16 @@ class MXQuantLinear(nn.Module):
                 x2 = x2.contiguous()
             ldx = x2.stride(0) if T > 1 else n
             bias = self.bias
+            if self.act_format is not None:
+                with torch.cuda.device(x.device):
+                    nbytes = lib.tg_qgemm_mx_act_workspace_size(T, m, n)
+                    ws = workspace(nbytes, x.device)
+                    call("tg_qgemm_mx_act", stream(), ptr(x2), DTYPES[x.dtype], T, ldx,
+                         ptr(self.qweight), ptr(self.scales), TG_FMT_MXFP4,
+                         ACT_FORMATS[self.act_format], m, n, ptr(bias),
+                         DTYPES[bias.dtype] if bias is not None else 0, ptr(y), DTYPES[x.dtype],
+                         m, ptr(ws), nbytes)
+                return y.reshape(*x.shape[:-1], m)
             with torch.cuda.device(x.device):
                 nbytes = lib.tg_qgemm_workspace_size(T, m, n)
                 ws = workspace(nbytes, x.device)

@@ -490,8 +490,9 @@ int tg_qgemm(void *stream, const void *X, int x_dtype, int T, int64_t ldx, const
  * call.  The same two regimes, the same TG_QGEMM switch, the same workspace
  * (tg_qgemm_workspace_size) and the same argument checks as tg_qgemm; stride_x
  * >= n and stride_y >= m are the row strides of X and Y.
- * Weights only: activations stay 16-bit and the block-scaled MFMA
- * instructions, which need both operands in low precision, are not used. */
+ * Weights only: activations stay 16-bit here; tg_qgemm_mx_act (A16, below) is
+ * the opt-in W4A8 path on the block-scaled MFMA instructions, which need both
+ * operands in low precision. */
 enum tg_weight_format { TG_FMT_MXFP4 = 1 };
 int tg_group_params_mx(void *stream, const float *W, int m, int n, int stride_w, int fmt,
                        float *scale, uint8_t *e8m0);
@@ -505,6 +506,63 @@ int tg_qgemm_mx(void *stream, const void *X, int x_dtype, int T, int64_t stride_
                 const int32_t *qweight, const uint8_t *scales_e8m0, int fmt, int m, int n,
                 const void *bias, int bias_dtype, void *Y, int y_dtype, int64_t stride_y, void *ws,
                 size_t ws_bytes);
+
+/* ---- A16: MXFP8 activations (new; opt-in W4A8 for MXFP4 checkpoints) --------
+ * `act_fmt` is a tg_act_format; TG_ACT_MXFP8 is its only value (anything else
+ * is rejected with act_fmt's argument index).  Elements are e4m3fn in the OCP
+ * encoding (bias 7, subnormals, largest finite 448 = 0x7e, no infinity; not
+ * fnuz), one shared E8M0 byte per 32 values.  Every f32 operation below is one
+ * correctly rounded operation in the order written.  Activations are finite;
+ * NaN and Inf are outside the contract.
+ *
+ * Quantiser (tg_quant_act_mx; X is T x n of x_dtype TG_F16 / TG_BF16 with row
+ * stride stride_x >= n, xq is T x n bytes with row stride stride_q >= n, xs is
+ * T x n/32 bytes, contiguous).  Blocks: 32 consecutive columns of one row;
+ * n % 32 == 0.
+ *   a = max |x| over the block, converted exactly to f32;
+ *   byte = max(exponent_field(a) - 8, 0), exponent_field the biased 8-bit field
+ *     of a's f32 encoding and 8 e4m3's emax (a == 0 and f32 subnormals: byte 0);
+ *     byte <= 246, so 255 (NaN) is never written;
+ *   t = x * 2^(127 - byte): exact, but for results below the f32 normal range,
+ *     which lie far below the smallest e4m3 tie 2^-10 and become zero either way;
+ *   q = t rounded to nearest, ties to even, onto the e4m3fn grid, the subnormals
+ *     (multiples of 2^-9 below 2^-6) included; |t| > 448 saturates to +-448
+ *     (|t| < 512 by construction, so the rounding never reaches the NaN code).
+ *   Sign: the sign bit of q is the sign bit of x, always: -0 and negative values
+ *     that round to zero give 0x80, which decodes to -0 and multiplies as zero.
+ * X may be a strided view; loads are 16 bytes wide where X and stride_x allow
+ * it and scalar otherwise, the stores of xq likewise.
+ *
+ * tg_qgemm_mx_act: Y (T x m, row stride stride_y >= m) = X^ * W^^T (+ bias).
+ * X^ is exactly tg_quant_act_mx's output decoded, float(e4m3(q)) * 2^(byte -
+ * 127); W^ is exactly tg_dequant_mx's TG_F32 output of the packed pair.  Both
+ * go to v_mfma_scale_f32_16x16x128_f8f6f4 as they lie in memory: no weight is
+ * decoded outside the matrix pipe.  Accumulation is f32 (inside a 128-value
+ * step in the instruction's own order, across steps in ascending k); the bias
+ * (m, nullable, TG_F16 / TG_BF16 / TG_F32) is added in f32; one rounding to
+ * y_dtype TG_F16 / TG_BF16 / TG_F32.  Bit-identical from call to call.
+ * One regime for every T (no TG_QGEMM switch): the activations are quantised
+ * once into the workspace, then a workgroup owns (16 rows up to T = 32, above
+ * 64) x 64 features and walks K in steps of 128; while the output tiles
+ * are fewer than ~512 workgroups K is split into S parts of at least 4 steps
+ * and a second kernel adds the partial sums [S][T][m] in ascending order, then
+ * the bias.  Requires n % 32 == 0 and (m * 4) % 32 == 0.
+ * Weight scale bytes 0 .. 254 are accepted.  The instruction applies both
+ * scales to the products exactly and produces f32 subnormals; a product below
+ * 2^-149 becomes zero and one above the f32 range becomes inf (measured:
+ * DESIGN.md "MXFP8 activations").
+ * tg_qgemm_mx_act_workspace_size(T, m, n): X^ with T rounded up to 16 and n
+ * to 128 (2048 + 64 bytes per 16 rows x 128 columns; the kernel keeps it in the
+ * instruction's operand order), plus S*T*m*4 bytes when S > 1, plus alignment
+ * slack; ws is never null. */
+enum tg_act_format { TG_ACT_MXFP8 = 1 };
+int tg_quant_act_mx(void *stream, const void *X, int x_dtype, int T, int64_t stride_x, int n,
+                    int act_fmt, uint8_t *xq, int64_t stride_q, uint8_t *xs);
+size_t tg_qgemm_mx_act_workspace_size(int T, int m, int n);
+int tg_qgemm_mx_act(void *stream, const void *X, int x_dtype, int T, int64_t stride_x,
+                    const int32_t *qweight, const uint8_t *scales_e8m0, int fmt, int act_fmt,
+                    int m, int n, const void *bias, int bias_dtype, void *Y, int y_dtype,
+                    int64_t stride_y, void *ws, size_t ws_bytes);
 
 #ifdef __cplusplus
 }
