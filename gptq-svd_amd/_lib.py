@@ -98,6 +98,13 @@ _SIGS = {
     "tg_qgemm_mx_act_workspace_size": ([_i, _i, _i], _sz),
     "tg_qgemm_mx_act": ([_vp, _vp, _i, _i, _i64, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _i64,
                          _vp, _sz], _i),
+    "tg_lrc_workspace_size": ([_i, _i, _i, _i, _i], _sz),
+    "tg_lrc_factor": ([_vp, _vp, _i, _i, _i64, _vp, _i, _i, _i64, _vp, _i, _i, _vp, _i64, _vp,
+                       _i64, _i, _vp, _vp, _vp, _vp, _sz], _i),
+    "tg_lr_down_workspace_size": ([_i, _i, _i], _sz),
+    "tg_lr_down": ([_vp, _vp, _i, _i, _i64, _vp, _i, _i, _i, _i64, _vp, _i64, _vp, _sz], _i),
+    "tg_lr_finish": ([_vp, _vp, _i64, _vp, _i64, _vp, _i, _i64, _i, _i, _i, _vp, _i, _vp, _i,
+                      _i64], _i),
 }
 
 EXPORTED = []

@@ -24,6 +24,13 @@ group_size 32): per linear only
 and the bias; W[:, j] = +-{0, .5, 1, 1.5, 2, 3, 4, 6}[code & 7] * scale[:, j // 32],
 the sign in bit 3 of the code.
 
+Low-rank correction (``quantize_model(lowrank=r)``): a corrected linear also has
+  ``<name>.lr_a`` (out, r) and ``<name>.lr_b`` (r, in), fp16 / bf16 / fp32,
+its effective weight being W + lr_a lr_b, and ``quantize_config.json`` records
+``"lowrank": r``.  Checkpoints without these tensors are read exactly as before.
+Loaders that do not know the two tensors (AutoGPTQ, GPTQModel) cannot apply
+the correction.
+
 ``load_quantized`` is the way back: it puts the packed tensors into
 ``qlinear.QuantLinear`` (``qlinear.MXQuantLinear`` for MXFP4) modules of a
 model, which run them without unpacking.
@@ -59,7 +66,14 @@ def save_quantized(path: str, model: torch.nn.Module, packed: Dict[str, Dict[str
     os.makedirs(path, exist_ok=True)
     sd = model.state_dict()
     tensors: Dict[str, torch.Tensor] = {}
+    lowrank = 0
     for name, t in packed.items():
+        if (t.get("lr_a") is None) != (t.get("lr_b") is None):
+            raise ValueError(f"{name}: lr_a and lr_b come together")
+        if t.get("lr_a") is not None:
+            tensors[f"{name}.lr_a"] = t["lr_a"].contiguous().cpu()
+            tensors[f"{name}.lr_b"] = t["lr_b"].contiguous().cpu()
+            lowrank = max(lowrank, int(t["lr_a"].shape[1]))
         if mx:
             if t["scales"].dtype != torch.uint8:
                 raise ValueError(f"{name}: MXFP4 scales must be uint8, got {t['scales'].dtype}")
@@ -92,6 +106,8 @@ def save_quantized(path: str, model: torch.nn.Module, packed: Dict[str, Dict[str
           "scale_dtype": str(scale_dtype).replace("torch.", "")}
     if mx:
         qc.update(sym=True, checkpoint_format="mxfp4", scale_dtype="e8m0")
+    if lowrank:
+        qc["lowrank"] = lowrank
     if extra_config:
         qc["truncgptq"] = extra_config
     with open(os.path.join(path, "quantize_config.json"), "w") as f:
@@ -112,6 +128,15 @@ def read_quantized(path: str):
     return tensors, qc
 
 
+def _lowrank_of(tensors: Dict[str, torch.Tensor], name: str, keys: Dict[str, str]):
+    """The (lr_a, lr_b) pair of a linear, or None; `keys` gains their names."""
+    keys.update(lr_a=f"{name}.lr_a", lr_b=f"{name}.lr_b")
+    a, b = tensors.get(keys["lr_a"]), tensors.get(keys["lr_b"])
+    if (a is None) != (b is None):
+        raise KeyError(f"{name}: lr_a and lr_b come together, the checkpoint holds one")
+    return None if a is None else (a, b)
+
+
 def _set_submodule(model: torch.nn.Module, name: str, new: torch.nn.Module) -> None:
     parent_name, _, leaf = name.rpartition(".")
     parent = model.get_submodule(parent_name) if parent_name else model
@@ -124,7 +149,8 @@ def load_quantized(model: torch.nn.Module, path: str, device=None,
     architecture, any weights) and return it: every ``nn.Linear`` whose
     ``<name>.qweight`` is in the checkpoint becomes a ``qlinear.QuantLinear``
     holding the packed tensors (bias kept, in the linear's dtype); every other
-    tensor is loaded as is.  ``quantize_config.json`` must be a static-group
+    tensor is loaded as is.  A linear with ``<name>.lr_a`` / ``<name>.lr_b`` gets
+    them as its low-rank correction.  ``quantize_config.json`` must be a static-group
     ``desc_act=false`` configuration with supported bits, and every ``g_idx``
     must be the trivial ``arange(in) // group`` map (act-order checkpoints are
     out of scope).  `device`: where the model is moved (default: it stays).
@@ -173,10 +199,12 @@ def load_quantized(model: torch.nn.Module, path: str, device=None,
             raise ValueError(f"{name}: the checkpoint and the model disagree about a bias")
         if bias is not None:
             bias = bias.to(lin.bias.dtype)
+        lowrank = _lowrank_of(tensors, name, keys)
         try:
             q = QuantLinear.from_packed(tensors[keys["qweight"]], tensors[keys["qzeros"]],
                                         tensors[keys["scales"]], bits, group, bias=bias,
-                                        g_idx=tensors[keys["g_idx"]], device=lin.weight.device)
+                                        g_idx=tensors[keys["g_idx"]], device=lin.weight.device,
+                                        lowrank=lowrank)
         except ValueError as e:
             raise ValueError(f"{name}: {e}") from None
         if (q.out_features, q.in_features) != (lin.out_features, lin.in_features):
@@ -214,10 +242,11 @@ def _load_mx(model: torch.nn.Module, tensors: Dict[str, torch.Tensor], qc: Dict[
             raise ValueError(f"{name}: the checkpoint and the model disagree about a bias")
         if bias is not None:
             bias = bias.to(lin.bias.dtype)
+        lowrank = _lowrank_of(tensors, name, keys)
         try:
             q = MXQuantLinear.from_packed(tensors[keys["qweight"]], tensors[keys["scales"]],
                                           bias=bias, device=lin.weight.device,
-                                          act_format=act_format)
+                                          act_format=act_format, lowrank=lowrank)
         except ValueError as e:
             raise ValueError(f"{name}: {e}") from None
         if (q.out_features, q.in_features) != (lin.out_features, lin.in_features):

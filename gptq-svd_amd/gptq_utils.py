@@ -28,6 +28,7 @@ __all__ = [
     "HessianAccumulator", "process_hessian_alt", "process_hessian", "Quantizer", "gptq_fwrd",
     "triton_process_block", "log_quantization_error", "next_power_of_2",
     "truncated_spectral_factor", "pack_quantized", "Sketcher", "process_sketch",
+    "lowrank_correction",
 ]
 
 
@@ -669,3 +670,78 @@ def pack_quantized(quantizer: Quantizer, codes: Optional[torch.Tensor] = None):
         call("tg_pack_zeros", stream(), ptr(zero), m, G, b, int(quantizer.sym), ptr(qzeros))
     scales = quantizer.scale.squeeze(-1).t().contiguous()
     return qweight, qzeros, scales
+
+
+# ---------------------------------------------------------------------------
+# A17  low-rank correction of the residual (new; DESIGN.md "Low-rank correction")
+# ---------------------------------------------------------------------------
+LOWRANK_MAX = 128
+
+
+def lowrank_correction(E: torch.Tensor, r: int, *, H: Optional[torch.Tensor] = None,
+                       factor: Optional[torch.Tensor] = None,
+                       perm: Optional[torch.Tensor] = None, dtype=torch.float32):
+    """The rank-r correction A B of the residual E = W - Wq (m x n) that
+    minimises tr((E - A B) H (E - A B)^T): (A, B, info), A (m x r) and B
+    (r x n) of ``dtype`` (float32, or float64 for checking), balanced per
+    direction by a power of two (tg_lrc_factor, include/truncgptq.h).
+
+    H is described by exactly one of
+      ``H``       the n x n Hessian itself (float64; the ``gptq`` mode), or
+      ``factor``  F (p x n, float64 or float32) with H = F^T F: R_x of
+                  process_hessian_alt together with its ``perm``
+                  (F[:, perm[j]] = R_x[:, j]), or the scaled sketch Y.
+    ``info``: ``mu`` (r float64, the captured eigenvalues of E H E^T, 0 for a
+    dropped direction), ``err0`` = tr(E H E^T), ``err1`` = err0 - sum(mu), the
+    weighted error that is left, and ``rank``, the number of directions kept
+    (those with mu_j > n 2^-52 mu_1).  One host sync."""
+    if E.dim() != 2:
+        raise ValueError("lowrank_correction: E must be a matrix")
+    m, n = E.shape
+    r = int(r)
+    if not 1 <= r <= LOWRANK_MAX:
+        raise ValueError(f"lowrank_correction: r must be in [1, {LOWRANK_MAX}], got {r}")
+    if r > min(m, n):
+        raise ValueError(f"lowrank_correction: r = {r} exceeds min(m, n) = {min(m, n)}")
+    if (H is None) == (factor is None):
+        raise ValueError("lowrank_correction: give exactly one of H and factor")
+    if H is not None and perm is not None:
+        raise ValueError("lowrank_correction: perm goes with factor, not with H")
+    if dtype not in (torch.float32, torch.float64):
+        raise ValueError("lowrank_correction: dtype must be float32 or float64")
+    F = H if factor is None else factor
+    if F.dim() != 2 or F.shape[1] != n or (H is not None and F.shape[0] != n):
+        raise ValueError(f"lowrank_correction: {'H' if H is not None else 'factor'} has shape "
+                         f"{tuple(F.shape)}, E has {n} columns")
+    _lib.require_cuda(E, "lowrank_correction E")
+    dev = E.device
+    Ed = E.to(torch.float32)
+    if Ed.stride(1) != 1:
+        Ed = Ed.contiguous()
+    Fd = F.to(device=dev)
+    if H is not None or Fd.dtype != torch.float32:
+        Fd = Fd.to(torch.float64)
+    if Fd.stride(1) != 1:
+        Fd = Fd.contiguous()
+    pd = None
+    if perm is not None:
+        pd = perm.to(device=dev, dtype=torch.int64).contiguous()
+        if pd.numel() != n or not torch.equal(torch.sort(pd).values,
+                                               torch.arange(n, device=dev)):
+            raise ValueError("lowrank_correction: perm must be a permutation of 0 .. n-1")
+    gram = int(H is not None)
+    p = Fd.shape[0]
+    A = torch.empty((m, r), dtype=dtype, device=dev)
+    B = torch.empty((r, n), dtype=dtype, device=dev)
+    out = torch.empty(r + 1, dtype=torch.float64, device=dev)       # mu, err0
+    rank = torch.empty(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        ws = workspace(_lib.lib.tg_lrc_workspace_size(m, n, p, r, gram), dev)
+        call("tg_lrc_factor", stream(), ptr(Ed), m, n, Ed.stride(0), ptr(Fd),
+             _lib.DTYPES[Fd.dtype], p, Fd.stride(0), ptr(pd), gram, r, ptr(A), A.stride(0),
+             ptr(B), B.stride(0), _lib.DTYPES[dtype], ptr(out), ptr(out[r:]), ptr(rank),
+             ptr(ws), ws.numel())
+    host = torch.cat((out, rank.to(torch.float64))).cpu().numpy()
+    mu, err0 = host[:r].copy(), float(host[r])
+    info = dict(mu=mu, err0=err0, err1=err0 - float(mu.sum()), rank=int(host[r + 1]))
+    return A, B, info

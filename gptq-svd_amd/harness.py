@@ -56,9 +56,9 @@ import torch
 from torch import nn
 
 from . import dist as tgdist
-from .gptq_utils import (HessianAccumulator, Quantizer, Sketcher, gptq_fwrd,
-                         log_quantization_error, pack_quantized, process_hessian,
-                         process_hessian_alt, process_sketch)
+from .gptq_utils import (LOWRANK_MAX, HessianAccumulator, Quantizer, Sketcher, gptq_fwrd,
+                         log_quantization_error, lowrank_correction, pack_quantized,
+                         process_hessian, process_hessian_alt, process_sketch)
 
 __all__ = ["get_layers", "get_sequenced_groups", "capture_initial_inputs", "quantize_model",
            "adaptive_eps", "StageClock", "check_factor_agrees", "run_and_record"]
@@ -335,7 +335,8 @@ def quantize_model(model: nn.Module, input_ids_list: Sequence[torch.Tensor], mod
                    staged: Optional[bool] = None, sketch_ratio: float = 4.0,
                    sketch_seed: Optional[int] = None, clip_search: bool = False,
                    clip_grid: int = 100, clip_steps: int = 80,
-                   weight_format: str = "int") -> Dict[str, Any]:
+                   weight_format: str = "int", lowrank: int = 0,
+                   lowrank_dtype: torch.dtype = torch.float16) -> Dict[str, Any]:
     """Quantise every sequenced linear of `model` in place (layer by layer).
 
     mode "eigh" = TruncGPTQ (process_hessian_alt + gptq_fwrd(use_triton=True));
@@ -366,6 +367,20 @@ def quantize_model(model: nn.Module, input_ids_list: Sequence[torch.Tensor], mod
     work), and with ``pack=True`` keeps ``qweight`` and the uint8 ``scales`` of
     each linear (``qzeros`` None).  Every ``layer_stats`` entry records the
     format.
+    `lowrank` (A17): r > 0 adds to every quantised linear the rank-r correction
+    A B of its residual W - Wq that minimises tr((W - Wq - A B) H (W - Wq - A B)^T)
+    (``lowrank_correction``), with H described by what the group's factorisation
+    already holds: R_x and perm in mode "eigh", the scaled sketch in mode "svd",
+    H itself in mode "gptq".  A and B are rounded to `lowrank_dtype` (float16,
+    bfloat16 or float32) and the weight written back is Wq + A B as the packed
+    forward applies it (``qlinear.add_lowrank``), so later layers calibrate on
+    what the packed model computes.  With ``pack=True`` the module's entry gains
+    ``lr_a`` (out, r) and ``lr_b`` (r, in); its ``layer_stats`` entry gains
+    ``lr_rank`` (directions kept), ``lr_err0`` and ``lr_err1`` (the weighted
+    error before and after, for the unrounded factors) and one line is logged.
+    r is capped at min(out, in) per module.  Works with `weight_format` and
+    `clip_search`; 0 (default) leaves the run bit for bit as it was; single
+    process only (ValueError before any work in the multi-GPU mode).
     `offload`: move each layer to `device` for its turn and back to the CPU
     afterwards (the reference's policy, quantize.py:101, :239); by default
     the model stays where it is (a whole 8B/70B model fits in 288 GB).
@@ -403,6 +418,17 @@ def quantize_model(model: nn.Module, input_ids_list: Sequence[torch.Tensor], mod
         if _world(pg)[0] > 1:
             raise ValueError("weight_format='mxfp4' is single-process")
         w_bits, group_size = 4, 32
+    lowrank = int(lowrank)
+    if not 0 <= lowrank <= LOWRANK_MAX:
+        raise ValueError(f"lowrank must be in [0, {LOWRANK_MAX}], got {lowrank}")
+    if lowrank:
+        if lowrank_dtype not in (torch.float16, torch.bfloat16, torch.float32):
+            raise ValueError(f"lowrank_dtype must be float16, bfloat16 or float32, got "
+                             f"{lowrank_dtype}")
+        if _world(pg)[0] > 1:
+            raise ValueError("lowrank is single-process")
+    # passed on only when the correction is on, so a run without it is unchanged
+    lr_kw = dict(lowrank=lowrank, lowrank_dtype=lowrank_dtype) if lowrank else {}
     # passed on only for MX, so an integer run is unchanged
     fmt_kw = dict(weight_format=weight_format) if weight_format != "int" else {}
     if not 0 <= clip_steps < clip_grid:
@@ -419,7 +445,7 @@ def quantize_model(model: nn.Module, input_ids_list: Sequence[torch.Tensor], mod
                              batch_size=batch_size, device=device, block_size=block_size,
                              pack=pack, offload=offload, pg=pg, early_stop=early_stop, clock=clock,
                              staged=staged, sketch_ratio=sketch_ratio, sketch_seed=sketch_seed,
-                             **clip_kw, **fmt_kw)
+                             **clip_kw, **fmt_kw, **lr_kw)
         return res
     t_start = time.time()
     world, rank = _world(pg)
@@ -506,6 +532,16 @@ def quantize_model(model: nn.Module, input_ids_list: Sequence[torch.Tensor], mod
             # the search's column weights, taken before H is freed
             qkw["col_weight"] = (H.float().square().sum(dim=0) if mode == "svd"
                                  else torch.diagonal(H).clone())
+        # what describes H to the low-rank correction stays alive through the
+        # per-module loop: R_x with perm (eigh), the scaled sketch (svd), H (gptq)
+        if not lowrank:
+            lr_h = None
+        elif mode == "eigh":
+            lr_h = dict(factor=R_x, perm=perm)
+        elif mode == "svd":
+            lr_h = dict(factor=H)
+        else:
+            lr_h = dict(H=H)
         del H
         if world > 1:
             check_factor_agrees(R, perm, pg)
@@ -523,11 +559,21 @@ def quantize_model(model: nn.Module, input_ids_list: Sequence[torch.Tensor], mod
             else:
                 Wq, k = gptq_fwrd(sub.weight.data.float(), R, q, perm,
                                   block_size=block_size, use_triton=(mode != "gptq"), R_x=R_x)
+            if lr_h is not None:
+                from .qlinear import add_lowrank
+                W = sub.weight.data.float()
+                lr_a, lr_b, lr_info = lowrank_correction(W - Wq.float(), min(lowrank, *W.shape),
+                                                         **lr_h)
+                lr_a, lr_b = lr_a.to(lowrank_dtype), lr_b.to(lowrank_dtype)
+                Wq = add_lowrank(Wq.float(), lr_a, lr_b)
+                del W
             sub.weight.copy_(Wq)
             full = f"layer_{i}.{name}"
             if pack:
                 qw, qz, sc = pack_quantized(q)
                 packed[qual.get(id(sub), full)] = dict(qweight=qw, qzeros=qz, scales=sc)
+                if lr_h is not None:
+                    packed[qual.get(id(sub), full)].update(lr_a=lr_a, lr_b=lr_b)
             dt = time.time() - t0
             used = k if mode != "gptq" else "N/A"
             logging.info(f"   {name: <15} | Rank: {str(used): <4} | Time: {dt:.2f}s")
@@ -541,6 +587,11 @@ def quantize_model(model: nn.Module, input_ids_list: Sequence[torch.Tensor], mod
                              f"{moved}/{q.clip_choice.numel()} groups clipped")
                 entry.update(clip_j0=j0, clip_j=j1, clip_moved=moved,
                              clip_groups=q.clip_choice.numel())
+            if lr_h is not None:
+                logging.info(f"   [LowRank] r={lr_a.shape[1]} kept {lr_info['rank']}: weighted "
+                             f"error {lr_info['err0']:.4e} -> {lr_info['err1']:.4e}")
+                entry.update(lr_rank=lr_info["rank"], lr_err0=lr_info["err0"],
+                             lr_err1=lr_info["err1"])
             stats.append(entry)
         if clock:
             clock.stop("quantize", ev)
@@ -694,6 +745,9 @@ def run_and_record(model: nn.Module, input_ids_list: Sequence[torch.Tensor], sav
         cfg.update(_clip_settings(kw))
     if kw.get("weight_format", "int") != "int":
         cfg.update(weight_format=kw["weight_format"], w_bits=4, group_size=32)
+    if kw.get("lowrank"):
+        cfg.update(lowrank=int(kw["lowrank"]),
+                   lowrank_dtype=str(kw.get("lowrank_dtype", torch.float16)).replace("torch.", ""))
     mid = getattr(getattr(model, "config", None), "_name_or_path", None)
     if mid:
         cfg["model_id"] = mid
@@ -736,6 +790,8 @@ def _packed_copy(model: nn.Module, res: Dict[str, Any], save_path: str,
     extra = {"mode": kw.get("mode", "eigh")}
     if kw.get("clip_search"):
         extra.update(_clip_settings(kw))
+    if kw.get("lowrank"):
+        extra["lowrank_dtype"] = str(kw.get("lowrank_dtype", torch.float16)).replace("torch.", "")
     if kw.get("weight_format", "int") == "mxfp4":
         save_quantized(path, model, res["packed"], 4, 32, True, extra_config=extra,
                        weight_format="mxfp4")

@@ -23,6 +23,12 @@ MXFP8 activations (A16, opt-in): ``MXQuantLinear(..., act_format="mxfp8")``
 quantises x to e4m3 with one E8M0 byte per 32 columns (``quantize_act_mx``,
 ``tg_quant_act_mx``) and multiplies on the block-scaled MFMA instruction
 (``tg_qgemm_mx_act``): W4A8, different numerics from the weights-only path.
+
+Low-rank correction (A17, opt-in): a layer quantised with ``lowrank=r`` carries
+``lr_a`` (out, r) and ``lr_b`` (r, in) beside its packed weight, and computes
+``y = x W^^T + (x lr_b^T) lr_a^T + bias`` in three calls: the packed GEMM with
+fp32 output and no bias, ``tg_lr_down`` and ``tg_lr_finish``.  Without the two
+buffers the forward is the single call it was.
 """
 from __future__ import annotations
 
@@ -35,7 +41,7 @@ from ._lib import (ACT_FORMATS, DTYPES, TG_FMT_MXFP4, call, lib, ptr, require_cu
                    workspace)
 
 __all__ = ["QuantLinear", "dequantize_packed", "MXQuantLinear", "dequantize_packed_mx",
-           "quantize_act_mx", "dequantize_act_mx"]
+           "quantize_act_mx", "dequantize_act_mx", "add_lowrank"]
 
 _BITS = (2, 3, 4, 8)
 
@@ -83,6 +89,84 @@ def dequantize_packed(qweight: torch.Tensor, qzeros: torch.Tensor, scales: torch
     return out
 
 
+# ---------------------------------------------------------------------------
+# Low-rank correction (A17)
+# ---------------------------------------------------------------------------
+_LR_DTYPES = (torch.float16, torch.bfloat16, torch.float32)
+
+
+def _check_lowrank(lowrank, m: int, n: int):
+    """(A, B) of a ``lowrank=`` argument, checked against the layer's shape."""
+    A, B = lowrank
+    if A.dim() != 2 or B.dim() != 2 or A.shape[0] != m or B.shape[1] != n \
+            or A.shape[1] != B.shape[0]:
+        raise ValueError(f"lowrank factors {tuple(A.shape)}, {tuple(B.shape)} do not fit a "
+                         f"({m}, {n}) weight")
+    if not 1 <= A.shape[1] <= 128:
+        raise ValueError(f"lowrank rank must be in [1, 128], got {A.shape[1]}")
+    if A.dtype not in _LR_DTYPES or B.dtype not in _LR_DTYPES:
+        raise ValueError("lowrank factors must be float16, bfloat16 or float32")
+    return A, B
+
+
+def _register_lowrank(mod: nn.Module, rank: int, dtype: torch.dtype, device) -> None:
+    """Buffers ``lr_a`` (out, r), ``lr_b`` (r, in) for rank > 0; the attributes
+    are None otherwise, like an absent bias."""
+    if rank:
+        if not 1 <= rank <= 128:
+            raise ValueError(f"lowrank must be in [0, 128], got {rank}")
+        if dtype not in _LR_DTYPES:
+            raise ValueError("lowrank_dtype must be float16, bfloat16 or float32")
+        mod.register_buffer("lr_a", torch.zeros((mod.out_features, rank), dtype=dtype,
+                                                device=device))
+        mod.register_buffer("lr_b", torch.zeros((rank, mod.in_features), dtype=dtype,
+                                                device=device))
+    else:
+        mod.lr_a = mod.lr_b = None
+
+
+def _lowrank_finish(x2: torch.Tensor, T: int, ldx: int, y32: torch.Tensor, lr_a: torch.Tensor,
+                    lr_b: torch.Tensor, bias: Optional[torch.Tensor], y: torch.Tensor) -> None:
+    """y = round(y32 + (x2 lr_b^T) lr_a^T + bias): tg_lr_down, tg_lr_finish.  Call
+    inside ``torch.cuda.device``."""
+    m, r = lr_a.shape
+    n = lr_b.shape[1]
+    if lr_a.stride(1) != 1 or lr_b.stride(1) != 1:
+        lr_a, lr_b = lr_a.contiguous(), lr_b.contiguous()
+    z = torch.empty((T, r), dtype=torch.float32, device=y.device)
+    nbytes = lib.tg_lr_down_workspace_size(T, r, n)
+    ws = workspace(nbytes, y.device)
+    call("tg_lr_down", stream(), ptr(x2), DTYPES[x2.dtype], T, ldx, ptr(lr_b), DTYPES[lr_b.dtype],
+         r, n, lr_b.stride(0), ptr(z), r, ptr(ws), nbytes)
+    call("tg_lr_finish", stream(), ptr(y32), y32.stride(0), ptr(z), r, ptr(lr_a),
+         DTYPES[lr_a.dtype], lr_a.stride(0), T, m, r, ptr(bias),
+         DTYPES[bias.dtype] if bias is not None else 0, ptr(y), DTYPES[y.dtype], y.stride(0))
+
+
+def add_lowrank(W: torch.Tensor, A: torch.Tensor, B: torch.Tensor,
+                dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """``W + A B`` as the packed forward applies it, as a dense (out, in) matrix:
+    each entry starts from float32 W[o, i] and adds A[o, j] B[j, i] in ascending j
+    as fp32 fmas, then rounds once to `dtype` (``tg_lr_finish`` with the output
+    features as its rows).  The harness writes this back for a layer quantised
+    with ``lowrank``, and ``dequantize(effective=True)`` returns it."""
+    require_cuda(W, "add_lowrank W")
+    m, n = W.shape
+    A, B = _check_lowrank((A, B), m, n)
+    if dtype not in _LR_DTYPES:
+        raise ValueError(f"dtype must be float16, bfloat16 or float32, got {dtype}")
+    dev = W.device
+    W32 = W.to(torch.float32).contiguous()
+    z = A.to(device=dev, dtype=torch.float32).contiguous()        # exact
+    Bt = B.to(device=dev).t().contiguous()                         # (in, r)
+    r = z.shape[1]
+    out = torch.empty((m, n), dtype=dtype, device=dev)
+    with torch.cuda.device(dev):
+        call("tg_lr_finish", stream(), ptr(W32), n, ptr(z), r, ptr(Bt), DTYPES[Bt.dtype], r, m, n,
+             r, None, 0, ptr(out), DTYPES[dtype], n)
+    return out
+
+
 class QuantLinear(nn.Module):
     """A linear layer whose weight stays packed.  The buffer names are the
     checkpoint's keys, so ``load_state_dict`` fills it.  ``module.to(dtype)``
@@ -91,7 +175,8 @@ class QuantLinear(nn.Module):
 
     def __init__(self, in_features: int, out_features: int, w_bits: int, group_size: int,
                  bias: bool = False, scale_dtype: torch.dtype = torch.float16,
-                 bias_dtype: torch.dtype = torch.float16, device=None):
+                 bias_dtype: torch.dtype = torch.float16, device=None, lowrank: int = 0,
+                 lowrank_dtype: torch.dtype = torch.float16):
         super().__init__()
         if w_bits not in _BITS:
             raise ValueError(f"w_bits must be one of {_BITS}, got {w_bits}")
@@ -116,14 +201,19 @@ class QuantLinear(nn.Module):
             self.register_buffer("bias", torch.zeros(out_features, dtype=bias_dtype, device=device))
         else:
             self.bias = None
+        _register_lowrank(self, int(lowrank), lowrank_dtype, device)
 
     @classmethod
     def from_packed(cls, qweight: torch.Tensor, qzeros: torch.Tensor, scales: torch.Tensor,
                     w_bits: int, group_size: int, bias: Optional[torch.Tensor] = None,
-                    g_idx: Optional[torch.Tensor] = None, device=None) -> "QuantLinear":
+                    g_idx: Optional[torch.Tensor] = None, device=None,
+                    lowrank=None) -> "QuantLinear":
         """From the packed tensors (a checkpoint's, or ``pack_quantized``'s).
-        `g_idx`, when given, must be the trivial ``arange(in) // group``."""
+        `g_idx`, when given, must be the trivial ``arange(in) // group``.
+        ``lowrank=(A, B)``: the correction's factors, (out, r) and (r, in)."""
         m, n, g = _shapes(qweight, qzeros, scales, w_bits, group_size)
+        if lowrank is not None:
+            lowrank = _check_lowrank(lowrank, m, n)
         if g_idx is not None:
             triv = torch.arange(n, dtype=torch.int64) // g
             if tuple(g_idx.shape) != (n,) or not torch.equal(g_idx.cpu().to(torch.int64), triv):
@@ -131,20 +221,33 @@ class QuantLinear(nn.Module):
                                  "(act-order checkpoints are not supported)")
         dev = device if device is not None else qweight.device
         q = cls(n, m, w_bits, group_size, bias=bias is not None, scale_dtype=scales.dtype,
-                bias_dtype=bias.dtype if bias is not None else torch.float16, device=dev)
+                bias_dtype=bias.dtype if bias is not None else torch.float16, device=dev,
+                lowrank=lowrank[0].shape[1] if lowrank is not None else 0,
+                lowrank_dtype=lowrank[0].dtype if lowrank is not None else torch.float16)
         q.qweight.copy_(qweight)
         q.qzeros.copy_(qzeros)
         q.scales.copy_(scales)
         if bias is not None:
             q.bias.copy_(bias.detach())
+        if lowrank is not None:
+            q.lr_a.copy_(lowrank[0].detach())
+            q.lr_b.copy_(lowrank[1].detach())
         return q
 
     def extra_repr(self) -> str:
+        lr = f", lowrank={self.lr_a.shape[1]}" if self.lr_a is not None else ""
         return (f"in_features={self.in_features}, out_features={self.out_features}, "
-                f"bits={self.w_bits}, group_size={self.group_size}, bias={self.bias is not None}")
+                f"bits={self.w_bits}, group_size={self.group_size}, "
+                f"bias={self.bias is not None}{lr}")
 
-    def dequantize(self, dtype: torch.dtype = torch.float16) -> torch.Tensor:
-        """The dense (out, in) weight."""
+    def dequantize(self, dtype: torch.dtype = torch.float16,
+                   effective: bool = False) -> torch.Tensor:
+        """The dense (out, in) weight; ``effective=True`` adds the low-rank
+        correction, W^ + lr_a lr_b (``add_lowrank``), when the layer has one."""
+        if effective and self.lr_a is not None:
+            W = dequantize_packed(self.qweight, self.qzeros, self.scales, self.w_bits,
+                                  self.group_size, torch.float32)
+            return add_lowrank(W, self.lr_a, self.lr_b, dtype)
         return dequantize_packed(self.qweight, self.qzeros, self.scales, self.w_bits,
                                  self.group_size, dtype)
 
@@ -167,14 +270,20 @@ class QuantLinear(nn.Module):
                 x2 = x2.contiguous()
             ldx = x2.stride(0) if T > 1 else n
             bias = self.bias
+            lr = self.lr_a is not None
+            # with a correction the GEMM leaves its fp32 sums; tg_lr_finish adds the bias
+            out = torch.empty((T, m), dtype=torch.float32, device=x.device) if lr else y
+            gb = None if lr else bias
             with torch.cuda.device(x.device):
                 nbytes = lib.tg_qgemm_workspace_size(T, m, n)
                 ws = workspace(nbytes, x.device)
                 call("tg_qgemm", stream(), ptr(x2), DTYPES[x.dtype], T, ldx, ptr(self.qweight),
                      ptr(self.qzeros), ptr(self.scales), DTYPES[self.scales.dtype], m, n,
-                     self.group_size, self.w_bits, ptr(bias),
-                     DTYPES[bias.dtype] if bias is not None else 0, ptr(y), DTYPES[x.dtype], m,
+                     self.group_size, self.w_bits, ptr(gb),
+                     DTYPES[gb.dtype] if gb is not None else 0, ptr(out), DTYPES[out.dtype], m,
                      ptr(ws), nbytes)
+                if lr:
+                    _lowrank_finish(x2, T, ldx, out, self.lr_a, self.lr_b, bias, y)
         return y.reshape(*x.shape[:-1], m)
 
 
@@ -273,7 +382,8 @@ class MXQuantLinear(nn.Module):
     w_bits, group_size = 4, 32
 
     def __init__(self, in_features: int, out_features: int, bias: bool = False,
-                 bias_dtype: torch.dtype = torch.float16, device=None, act_format=None):
+                 bias_dtype: torch.dtype = torch.float16, device=None, act_format=None,
+                 lowrank: int = 0, lowrank_dtype: torch.dtype = torch.float16):
         super().__init__()
         _check_act_format(act_format)
         self.act_format = act_format
@@ -290,29 +400,44 @@ class MXQuantLinear(nn.Module):
             self.register_buffer("bias", torch.zeros(out_features, dtype=bias_dtype, device=device))
         else:
             self.bias = None
+        _register_lowrank(self, int(lowrank), lowrank_dtype, device)
 
     @classmethod
     def from_packed(cls, qweight: torch.Tensor, scales: torch.Tensor,
                     bias: Optional[torch.Tensor] = None, device=None,
-                    act_format=None) -> "MXQuantLinear":
-        """From the packed pair (a checkpoint's, or ``pack_quantized``'s)."""
+                    act_format=None, lowrank=None) -> "MXQuantLinear":
+        """From the packed pair (a checkpoint's, or ``pack_quantized``'s).
+        ``lowrank=(A, B)``: the correction's factors, (out, r) and (r, in)."""
         m, n = _shapes_mx(qweight, scales)
+        if lowrank is not None:
+            lowrank = _check_lowrank(lowrank, m, n)
         dev = device if device is not None else qweight.device
         q = cls(n, m, bias=bias is not None,
                 bias_dtype=bias.dtype if bias is not None else torch.float16, device=dev,
-                act_format=act_format)
+                act_format=act_format,
+                lowrank=lowrank[0].shape[1] if lowrank is not None else 0,
+                lowrank_dtype=lowrank[0].dtype if lowrank is not None else torch.float16)
         q.qweight.copy_(qweight)
         q.scales.copy_(scales)
         if bias is not None:
             q.bias.copy_(bias.detach())
+        if lowrank is not None:
+            q.lr_a.copy_(lowrank[0].detach())
+            q.lr_b.copy_(lowrank[1].detach())
         return q
 
     def extra_repr(self) -> str:
+        lr = f", lowrank={self.lr_a.shape[1]}" if self.lr_a is not None else ""
         return (f"in_features={self.in_features}, out_features={self.out_features}, "
-                f"format=mxfp4, bias={self.bias is not None}, act_format={self.act_format}")
+                f"format=mxfp4, bias={self.bias is not None}, act_format={self.act_format}{lr}")
 
-    def dequantize(self, dtype: torch.dtype = torch.float16) -> torch.Tensor:
-        """The dense (out, in) weight."""
+    def dequantize(self, dtype: torch.dtype = torch.float16,
+                   effective: bool = False) -> torch.Tensor:
+        """The dense (out, in) weight; ``effective=True`` adds the low-rank
+        correction, W^ + lr_a lr_b (``add_lowrank``), when the layer has one."""
+        if effective and self.lr_a is not None:
+            return add_lowrank(dequantize_packed_mx(self.qweight, self.scales, torch.float32),
+                               self.lr_a, self.lr_b, dtype)
         return dequantize_packed_mx(self.qweight, self.scales, dtype)
 
     @torch.no_grad()
@@ -334,21 +459,30 @@ class MXQuantLinear(nn.Module):
                 x2 = x2.contiguous()
             ldx = x2.stride(0) if T > 1 else n
             bias = self.bias
+            lr = self.lr_a is not None
+            # with a correction the GEMM leaves its fp32 sums; tg_lr_finish adds the bias.
+            # Z = x lr_b^T always comes from the 16-bit x, under act_format too.
+            out = torch.empty((T, m), dtype=torch.float32, device=x.device) if lr else y
+            gb = None if lr else bias
             if self.act_format is not None:
                 with torch.cuda.device(x.device):
                     nbytes = lib.tg_qgemm_mx_act_workspace_size(T, m, n)
                     ws = workspace(nbytes, x.device)
                     call("tg_qgemm_mx_act", stream(), ptr(x2), DTYPES[x.dtype], T, ldx,
                          ptr(self.qweight), ptr(self.scales), TG_FMT_MXFP4,
-                         ACT_FORMATS[self.act_format], m, n, ptr(bias),
-                         DTYPES[bias.dtype] if bias is not None else 0, ptr(y), DTYPES[x.dtype],
+                         ACT_FORMATS[self.act_format], m, n, ptr(gb),
+                         DTYPES[gb.dtype] if gb is not None else 0, ptr(out), DTYPES[out.dtype],
                          m, ptr(ws), nbytes)
+                    if lr:
+                        _lowrank_finish(x2, T, ldx, out, self.lr_a, self.lr_b, bias, y)
                 return y.reshape(*x.shape[:-1], m)
             with torch.cuda.device(x.device):
                 nbytes = lib.tg_qgemm_workspace_size(T, m, n)
                 ws = workspace(nbytes, x.device)
                 call("tg_qgemm_mx", stream(), ptr(x2), DTYPES[x.dtype], T, ldx, ptr(self.qweight),
-                     ptr(self.scales), TG_FMT_MXFP4, m, n, ptr(bias),
-                     DTYPES[bias.dtype] if bias is not None else 0, ptr(y), DTYPES[x.dtype], m,
+                     ptr(self.scales), TG_FMT_MXFP4, m, n, ptr(gb),
+                     DTYPES[gb.dtype] if gb is not None else 0, ptr(out), DTYPES[out.dtype], m,
                      ptr(ws), nbytes)
+                if lr:
+                    _lowrank_finish(x2, T, ldx, out, self.lr_a, self.lr_b, bias, y)
         return y.reshape(*x.shape[:-1], m)

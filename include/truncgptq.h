@@ -564,6 +564,74 @@ int tg_qgemm_mx_act(void *stream, const void *X, int x_dtype, int T, int64_t str
                     int m, int n, const void *bias, int bias_dtype, void *Y, int y_dtype,
                     int64_t stride_y, void *ws, size_t ws_bytes);
 
+/* ---- A17: low-rank correction of the quantisation residual (new; absent in
+ * the reference, which writes back dense FP16) -------------------------------
+ * The best rank-r correction A B of E = W - Wq (m x n f32, row stride stride_e)
+ * under the solver's objective, min tr((E - A B) H (E - A B)^T): A B = Q Q^T E
+ * with Q the top-r eigenvectors of K = E H E^T (LoRC / LQER / QERA; DESIGN.md
+ * "Low-rank correction").  H comes in one of two forms:
+ *   gram = 0: a factor F (p x n, row stride stride_f, f_dtype TG_F64 or TG_F32,
+ *             converted exactly to f64) with H = Fg^T Fg, Fg[:, perm[j]] =
+ *             F[:, j]; perm (n int64, a permutation; null = identity) lets R_x
+ *             be passed as process_hessian_alt returns it, and the scaled
+ *             sketch Y goes in as it is (TG_F32, no perm).  M = E Fg^T (m x p);
+ *             m <= p: K = M M^T, Q its eigenvectors; m > p: K = M^T M with
+ *             eigenpairs (mu, P), Q = M P mu^-1/2.  The eigenproblem has order
+ *             min(m, p).
+ *   gram = 1: F is H itself (n x n f64, row stride stride_f; p is ignored,
+ *             perm must be null); K = (E H) E^T, m x m.
+ * 1 <= r <= 128 and r <= min(m, n).  Everything runs in FP64 on the library's
+ * GEMM, SYRK and eigensolver (tg_eigh_values, tg_eigh_vectors_range; the call
+ * synchronises the stream where they do).
+ * Outputs: A0 = Q, B0 = Q^T E, balanced per direction by the power of two
+ * s_j = 2^rint(log2(max|B0_j| / max|A0_j|) / 2): A[:, j] = A0_j s_j (m x r, row
+ * stride stride_a), B[j, :] = B0_j / s_j (r x n, row stride stride_b), both of
+ * ab_dtype TG_F32 (one rounding of the f64 value) or TG_F64 (what the tests
+ * compare).  Directions with mu_j <= n 2^-52 mu_1, and directions past
+ * min(m, p), come back as zero columns of A and zero rows of B, with mu_j = 0.
+ * mu (r doubles, descending), err0 = tr K, and rank (int32, the number of kept
+ * directions) are device memory; the weighted error after the correction is
+ * err0 - sum(mu).  Deterministic. */
+size_t tg_lrc_workspace_size(int m, int n, int p, int r, int gram);
+int tg_lrc_factor(void *stream, const float *E, int m, int n, int64_t stride_e, const void *F,
+                  int f_dtype, int p, int64_t stride_f, const int64_t *perm, int gram, int r,
+                  void *A, int64_t stride_a, void *B, int64_t stride_b, int ab_dtype, double *mu,
+                  double *err0, int32_t *rank, void *ws, size_t ws_bytes);
+
+/* The correction at inference: Y = X W^^T + (X B^T) A^T + bias, beside the
+ * packed GEMM and independent of its format.  The caller runs tg_qgemm /
+ * tg_qgemm_mx / tg_qgemm_mx_act with y_dtype TG_F32 and no bias into Y32, then
+ *   tg_lr_down:   Z (T x r f32, row stride stride_z) = X B^T, X (T x n, TG_F16 /
+ *                 TG_BF16, row stride stride_x), B (r x n, TG_F16 / TG_BF16 /
+ *                 TG_F32, row stride stride_b); 1 <= r <= 128, n % 8 == 0;
+ *   tg_lr_finish: Y[t, o] = round(Y32[t, o] + sum_j Z[t, j] A[o, j] + bias[o]),
+ *                 Y32 (T x m f32), A (m x r, TG_F16 / TG_BF16 / TG_F32), bias (m,
+ *                 nullable, the same three types), Y (T x m, row stride stride_y
+ *                 >= m) of y_dtype TG_F16 / TG_BF16 / TG_F32; Y may be Y32.
+ * Numerics: X, B and A are converted exactly to f32 and every product and sum
+ * is an f32 fma.  tg_lr_finish starts from Y32[t, o], adds the terms in
+ * ascending j, then the bias, and rounds once.  tg_lr_down sums k in a fixed
+ * order that depends on the regime and on (T, r, n) only; both calls are
+ * bit-identical from call to call (no atomics).
+ * tg_lr_down has two regimes (TG_LR_DOWN = auto | gemv | mfma, read per call;
+ * gemv with T > 16 is an argument error, -4): gemv (T <= 16, the auto choice
+ * there), one wave per row of B over a K chunk of a multiple of 512 values; mfma,
+ * a 128 x 32 tile of Z per workgroup on v_mfma_f32_32x32x2_f32 with K slabs of
+ * 32.  Both split K until about 512 workgroups run (gemv: chunks of at least
+ * 512 values; mfma: at least 256); with S > 1 splits the partial sums [S][T][r]
+ * go to the workspace and are added in ascending split order.  16-byte loads
+ * are taken from X, B and A where the pointer and the row stride allow them
+ * (16-bit: stride % 8 == 0; f32: stride % 4 == 0), scalar loads otherwise.
+ * tg_lr_down_workspace_size(T, r, n): S*T*r*4 bytes (+ alignment slack) for the
+ * larger S of the regimes that take T, 0 when that is 1. */
+size_t tg_lr_down_workspace_size(int T, int r, int n);
+int tg_lr_down(void *stream, const void *X, int x_dtype, int T, int64_t stride_x, const void *B,
+               int b_dtype, int r, int n, int64_t stride_b, float *Z, int64_t stride_z, void *ws,
+               size_t ws_bytes);
+int tg_lr_finish(void *stream, const float *Y32, int64_t stride_y32, const float *Z,
+                 int64_t stride_z, const void *A, int a_dtype, int64_t stride_a, int T, int m,
+                 int r, const void *bias, int bias_dtype, void *Y, int y_dtype, int64_t stride_y);
+
 #ifdef __cplusplus
 }
 #endif
