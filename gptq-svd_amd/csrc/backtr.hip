@@ -1398,8 +1398,6 @@ __global__ __launch_bounds__(64 * Q1W) void q1_lds_kernel(Q1LArgs a) {
 
 namespace tg {
 
-int sb_smax(int n);
-
 // ops: host-built step list; dev: >= ops.size() * sizeof(Q1Op) + FEW_HDR
 // bytes of device scratch (control words: step counter, timeout flag, bt_few's
 // XCD election [2..4], q1_lds arrivals [5], bt_few stats [8..23], q1_lds's XCD
@@ -1407,251 +1405,251 @@ int sb_smax(int n);
 constexpr int FEW_HDR = 1024;
 constexpr int FEW_SLABS = 8;  // 16-column slabs of the LDS-resident kernels: k <= 128
 static_assert(64 + 16 * FEW_SLABS <= FEW_HDR / 4, "slab counters fit the header");
-static size_t few_ops_bytes(const SbPlan &pl) {
-  size_t c = 0;
-  for (const SbPanel &P : pl.panels) c += size_t(P.nl);
-  return (FEW_HDR + c * sizeof(Q1Op) + 255) & ~size_t(255);
-}
-static int few_nsub(const SbPlan &pl) {  // + 1: sub-chunks are row-aligned, not panel-aligned
-  return pl.single && !pl.panels.empty() ? cdiv(pl.panels[0].m, Q1S) + 1 : 0;
-}
-// Column slabs (k > 16: TG_BT_SLABS=0 keeps bt_few for k = 17 .. 32): both
-// LDS kernels take 16 columns a workgroup, slabs side by side in blockIdx.y,
-// as many a launch as leave every workgroup a CU of its own (their spins need
-// all resident); q1_lds's at most Q1_SLABS at once (partials per slab)
-constexpr int Q1_SLABS = 3;
-static int xcd_all_cus() {
+constexpr int Q1_SLABS = 3;   // slabs a q1_lds launch at most (partials per slab)
+
+// Everything sb_apply_few does, decided once: the development switches (read
+// per call, here only), the device geometry, the kernel forms and grids, the
+// scratch layout.
+FewPlan few_plan(const SbPlan &pl, int n, int k) {
+  FewPlan p;
+  if (k < 1) return p;
+  p.n = n, p.k = k;
   const XcdInfo x = xcd_info();
-  return x.xcds * x.cus_per_xcd;
-}
-static bool few_slabs(int k) {
-  if (k <= 16) return false;
-  const char *e = getenv("TG_BT_SLABS");  // development switch, read per call
-  return !(e && e[0] == '0');
-}
-static int q1_conc(int n, int k) {
-  if (!few_slabs(k)) return 1;
-  return std::max(1, std::min({cdiv(k, 16), Q1_SLABS, xcd_all_cus() / std::max(1, cdiv(n, Q1R))}));
-}
-static size_t few_part_bytes(const SbPlan &pl, int n, int k) {
-  if (!pl.single || pl.panels.empty()) return 0;
-  const size_t lds_form = size_t(q1_conc(n, k)) * 2 * cdiv(n, Q1R) * 512 * sizeof(double);
-  return std::max(size_t(few_nsub(pl)) * SB_B * SB_B * sizeof(double), lds_form);
-}
-// + one progress word per Q2 sweep group (n / 32 + 1) and column slab, 16-byte padded
-size_t sb_apply_few_scratch(const SbPlan &pl, int n, int k) {
-  const size_t slabs = few_slabs(k) ? size_t(cdiv(k, 16)) : 1;
-  return few_ops_bytes(pl) + few_part_bytes(pl, n, k) +
-         ((size_t(n / QB + 1) * slabs * 4 + 15) & ~size_t(15));
-}
-// can sb_apply_few take k columns?  k <= 32 always (bt_few_kernel); up to 128
-// when the LDS-resident kernels fit (single-level plans, n / 128 workgroups <=
-// CUs) in at most 4 launches of the two: each launch is a chain of n / 32
-// dependent steps whatever its slabs, so past that the level-by-level
-// sb_apply_q2 / sb_apply_q1 are faster (measured: n = 28,672, k = 102 in 7 + 7
-// launches 201.7 ms against 109.5 ms; n = 4096, k = 100 in 1 + 3: 7.9 against
-// 11.1 ms; n = 14,336, k = 51 in 2 + 2: 29.4 against 39.9 ms)
-bool sb_apply_few_ok(const SbPlan &pl, int n, int k) {
-  if (k < 1) return false;
-  if (k <= 32) return true;
-  const int cus = xcd_all_cus(), wq = cdiv(cdiv(n - 2, QB), QW), w1 = cdiv(n, Q1R);
-  if (!few_slabs(k) || k > 16 * FEW_SLABS || !pl.single || n <= 2 || wq > cus || w1 > cus)
-    return false;
-  const int ns = cdiv(k, 16);
-  return cdiv(ns, cus / wq) + cdiv(ns, q1_conc(n, k)) <= 4;
+  const int cus = x.xcds * x.cus_per_xcd;
+  const auto sw = [](const char *v) { const char *e = getenv(v); return e ? e[0] : '\0'; };
+  // Column slabs (k > 16: TG_BT_SLABS=0 keeps bt_few for k = 17 .. 32): both
+  // LDS kernels take 16 columns a workgroup, slabs side by side in blockIdx.y,
+  // as many a launch (c2, c1) as leave every workgroup a CU of its own (their
+  // spins need all resident)
+  p.slabs = k > 16 && sw("TG_BT_SLABS") != '0';
+  p.nslab = p.slabs ? cdiv(k, 16) : 1;
+  for (const SbPanel &P : pl.panels) p.nops += P.nl;
+  p.smax = sb_smax(n);
+  p.ng2 = n > 2 ? cdiv(n - 2, QB) : 0;
+  p.nlev2 = n > 2 ? p.smax + p.ng2 - 1 : 0;
+  // Q2 with Z in LDS (TG_BT_Q2_LDS=0: the level-by-level Q2 inside
+  // bt_few_kernel, TG_BT_Q2_WAVE=1: its wavefront form): workgroups of QW pair
+  // columns, one per CU by their LDS, so at most the device's CUs; one
+  // 16-column block each (with two, registers spill at the 256-VGPR cap of two
+  // waves per SIMD), so k > 16 only in column slabs
+  p.Wq = cdiv(p.ng2, QW);
+  const bool wave = sw("TG_BT_Q2_WAVE") == '1';
+  const bool q2l = sw("TG_BT_Q2_LDS") != '0' && !wave && p.nlev2 > 0 && (k <= 16 || p.slabs) &&
+                   p.Wq <= cus;
+  p.q2 = wave ? FewQ2::Wave : q2l ? FewQ2::Lds : FewQ2::InFew;
+  p.c2 = q2l ? std::max(1, std::min(p.nslab, cus / p.Wq)) : 1;
+  // Q1 with Z in LDS as well (single-level plans; TG_BT_Q1_LDS=0: bt_few's):
+  // n <= 4096 and k <= 16: the workgroups of one XCD, else one per CU of the
+  // device.  TG_BT_Q1_LDS=2 (tests): the XCD form on a grid of W1 only, spread
+  // over the XCDs, so the election comes up short and bt_few's Q1 runs
+  p.W1 = cdiv(n, Q1R);
+  const char q1s = sw("TG_BT_Q1_LDS");
+  const bool one_xcd = p.W1 <= x.cus_per_xcd && k <= 16;
+  const bool q1l = q2l && q1s != '0' && pl.single && p.nops > 0 && (one_xcd || p.W1 <= cus);
+  p.q1 = !q1l ? FewQ1::InFew : one_xcd ? FewQ1::LdsXcd : FewQ1::LdsDevice;
+  p.q1_short = q1s == '2';
+  p.G1 = p.q1_short ? p.W1 : p.W1 * x.xcds;
+  p.c1 = p.slabs ? std::max(1, std::min({p.nslab, Q1_SLABS, cus / std::max(1, p.W1)})) : 1;
+  // bt_few_kernel: one wave per Q2 block of the widest level, one workgroup per
+  // TSQR chunk or row-aligned sub-chunk (+ 1: not panel-aligned).  The workers
+  // (a CU each: BtShared fills the LDS) must all be resident: in the XCD form at
+  // most one XCD's CUs (the loops take further sub-chunks in turn), W on each XCD
+  const bool parts = pl.single && !pl.panels.empty();
+  const int nsub = parts ? cdiv(pl.panels[0].m, Q1S) + 1 : 0;
+  p.W = std::min(256, std::max({1, cdiv(p.smax, BW), pl.ncmax, nsub}));
+  if (TG_BT_XCD) p.W = std::min(p.W, x.cus_per_xcd);
+  p.grid = TG_BT_XCD ? x.xcds * p.W : p.W;
+  // scratch: header, ops | partials (bt_few's per sub-chunk, q1_lds's 2 x W1 x 512
+  // per slab of a launch) | a progress word per Q2 sweep group and column slab
+  p.part_off = (FEW_HDR + size_t(p.nops) * sizeof(Q1Op) + 255) & ~size_t(255);
+  const size_t part = std::max(size_t(nsub) * SB_B * SB_B, size_t(p.c1) * 2 * p.W1 * 512);
+  p.flag_off = p.part_off + (parts ? part * sizeof(double) : 0);
+  p.total = p.flag_off + ((size_t(n / QB + 1) * p.nslab * 4 + 15) & ~size_t(15));
+  // k <= 32 always (bt_few_kernel takes what the LDS kernels do not); up to 128
+  // when both LDS-resident kernels run (the switches allow them, single-level
+  // plans, n / 128 workgroups <= CUs) in at most 4 launches of the two: each
+  // launch is a chain of n / 32 dependent steps whatever its slabs, so past
+  // that the level-by-level sb_apply_q2 / sb_apply_q1 are faster (measured:
+  // n = 28,672, k = 102 in 7 + 7 launches 201.7 ms against 109.5 ms; n = 4096,
+  // k = 100 in 1 + 3: 7.9 against 11.1 ms; n = 14,336, k = 51 in 2 + 2: 29.4
+  // against 39.9 ms)
+  p.ok = k <= 32 || (k <= 16 * FEW_SLABS && p.q2 == FewQ2::Lds && p.q1 != FewQ1::InFew &&
+                     cdiv(p.nslab, p.c2) + cdiv(p.nslab, p.c1) <= 4);
+  return p;
 }
 
-hipError_t sb_apply_few(hipStream_t st, int n, double *Z, int k, const SbPlan &pl,
-                        const SbBufs &b, void *dev, bool *timed_out) {
-  *timed_out = false;
-  if (!sb_apply_few_ok(pl, n, k)) return hipErrorInvalidValue;
-  const bool slabs = few_slabs(k);
-  const int nslab = slabs ? cdiv(k, 16) : 1;
-  std::vector<Q1Op> ops;
+struct FewDev {  // the plan's scratch, carved, and the spin timeout
+  unsigned *cnt;
+  Q1Op *ops;
+  double *part;
+  unsigned *colflag;
+  unsigned long long timeout;
+};
+
+// Copy the first `words` control words back, sync (the uploaded ops are read
+// before their host copy goes) and report the timeout flag.
+static hipError_t few_flags(hipStream_t st, const FewDev &d, unsigned *h, int words,
+                            bool *timed_out) {
+  hipError_t e = hipMemcpyAsync(h, d.cnt, words * sizeof(unsigned), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e == hipSuccess) *timed_out = h[1] != 0u;
+  return e;
+}
+
+// Zero the header and upload the step list (panels last to first, levels top down).
+static hipError_t few_upload(hipStream_t st, const SbPlan &pl, const FewDev &d,
+                             std::vector<Q1Op> &ops) {
   for (auto it = pl.panels.rbegin(); it != pl.panels.rend(); ++it)
     for (int l = it->nl - 1; l >= 0; --l) {
       const SbLevel &L = it->L[l];
       ops.push_back(Q1Op{it->r0, L.rows, L.nc, l, int(L.yoff), int(L.toff)});
     }
-  unsigned *cnt = static_cast<unsigned *>(dev);
-  Q1Op *dops = reinterpret_cast<Q1Op *>(static_cast<char *>(dev) + FEW_HDR);
-  hipError_t e = hipMemsetAsync(cnt, 0, FEW_HDR, st);
+  const hipError_t e = hipMemsetAsync(d.cnt, 0, FEW_HDR, st);
+  if (e != hipSuccess || ops.empty()) return e;
+  return hipMemcpyAsync(d.ops, ops.data(), ops.size() * sizeof(Q1Op), hipMemcpyHostToDevice, st);
+}
+
+// q2_lds_kernel: c2 column slabs a launch.
+static hipError_t few_q2_lds(hipStream_t st, double *Z, const FewPlan &fp, const SbBufs &b,
+                             const FewDev &d) {
+  hipError_t e =
+      hipMemsetAsync(d.colflag, 0, ((size_t(fp.ng2) * fp.nslab * 4 + 15) & ~size_t(15)), st);
   if (e != hipSuccess) return e;
-  if (!ops.empty()) {
-    e = hipMemcpyAsync(dops, ops.data(), ops.size() * sizeof(Q1Op), hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) return e;
-  }
-  const int nsw = n - 2;
-  BtArgs a{};
-  a.Z = Z;
-  a.n = n;
-  a.k = k;
-  a.V2 = b.V2;
-  a.T2 = b.T2;
-  a.smax = sb_smax(n);
-  a.ng2 = nsw > 0 ? cdiv(nsw, QB) : 0;
-  a.nlev2 = nsw > 0 ? a.smax + a.ng2 - 1 : 0;
-  a.Y = b.Y;
-  a.T = b.T;
-  a.ops = dops;
-  a.nops = int(ops.size());
-  a.single = pl.single ? 1 : 0;
-  a.part = reinterpret_cast<double *>(static_cast<char *>(dev) + few_ops_bytes(pl));
-  a.cnt = cnt;
-  a.timeout = spin_timeout_ticks("TG_BT_TIMEOUT_TICKS");
-  a.colflag = reinterpret_cast<unsigned *>(static_cast<char *>(dev) + few_ops_bytes(pl) +
-                                           few_part_bytes(pl, n, k));
-  {
-    const char *qw = getenv("TG_BT_Q2_WAVE");  // development switch, read per call
-    a.q2_wave = (qw && qw[0] == '1') ? 1 : 0;
-  }
-  if (a.q2_wave && a.ng2 > 0) {
-    e = hipMemsetAsync(a.colflag, 0, ((size_t(a.ng2) * 4 + 15) & ~size_t(15)), st);
-    if (e != hipSuccess) return e;
-  }
-  // Q2 with Z in LDS (q2_lds_kernel; TG_BT_Q2_LDS=0: the level-by-level Q2
-  // inside bt_few_kernel): one workgroup of QW pair columns per CU, all
-  // resident (one per CU by their LDS), so at most one per CU of the device
-  const XcdInfo xq = xcd_info();
-  {
-    const char *ql = getenv("TG_BT_Q2_LDS");  // development switch, read per call
-    const int Wq = cdiv(a.ng2, QW);
-    // (one 16-column block a workgroup: with two, registers spill at the
-    // 256-VGPR cap of two waves per SIMD; k > 16 in column slabs, or with
-    // TG_BT_SLABS=0 bt_few's Q2 for k = 17 .. 32)
-    const bool q2l = !(ql && ql[0] == '0') && !a.q2_wave && a.nlev2 > 0 && (k <= 16 || slabs) &&
-                     Wq <= xq.xcds * xq.cus_per_xcd;
-    if (!q2l && k > 32) return hipErrorInvalidValue;
-    if (q2l) {
-      e = hipMemsetAsync(a.colflag, 0, ((size_t(a.ng2) * nslab * 4 + 15) & ~size_t(15)), st);
-      if (e != hipSuccess) return e;
-      Q2LArgs qa{Z, n, k, b.V2, b.T2, a.smax, a.ng2, a.colflag, cnt + 1, a.timeout, 0};
-      const int c2 = std::max(1, std::min(nslab, xq.xcds * xq.cus_per_xcd / Wq));
-      auto tq = prof_begin(st, PROF_Q2, 0.0, 0.0);
+  Q2LArgs qa{Z, fp.n, fp.k, b.V2, b.T2, fp.smax, fp.ng2, d.colflag, d.cnt + 1, d.timeout, 0};
+  auto tq = prof_begin(st, PROF_Q2, 0.0, 0.0);
 #if TG_Q2L_STATS
-      {
-        const unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        (void)hipMemcpyToSymbolAsync(HIP_SYMBOL(g_q2l_stats), z, sizeof(z), 0,
-                                     hipMemcpyHostToDevice, st);
-      }
+  {
+    const unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    (void)hipMemcpyToSymbolAsync(HIP_SYMBOL(g_q2l_stats), z, sizeof(z), 0,
+                                 hipMemcpyHostToDevice, st);
+  }
 #endif
-      for (qa.slab0 = 0; qa.slab0 < nslab; qa.slab0 += c2) {
-        hipLaunchKernelGGL(q2_lds_kernel<1>, dim3(Wq, std::min(c2, nslab - qa.slab0)), dim3(64 * QW),
-                           0, st, qa);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-      }
-      prof_end(st, tq);
+  for (qa.slab0 = 0; qa.slab0 < fp.nslab; qa.slab0 += fp.c2) {
+    hipLaunchKernelGGL(q2_lds_kernel<1>, dim3(fp.Wq, std::min(fp.c2, fp.nslab - qa.slab0)),
+                       dim3(64 * QW), 0, st, qa);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  prof_end(st, tq);
 #if TG_Q2L_STATS
-      {
-        unsigned long long h[8];
-        (void)hipStreamSynchronize(st);
-        (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_q2l_stats), sizeof(h));
-        const double nbk = double(h[4] ? h[4] : 1);
-        fprintf(stderr, "q2_lds n=%d: %llu blocks; cycles per block: wait %.0f, tile+V %.0f, "
-                "mfma %.0f, store+publish %.0f\n", n, h[4], h[0] / nbk, h[1] / nbk, h[2] / nbk,
-                h[3] / nbk);
-      }
+  {
+    unsigned long long h[8];
+    (void)hipStreamSynchronize(st);
+    (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_q2l_stats), sizeof(h));
+    const double nbk = double(h[4] ? h[4] : 1);
+    fprintf(stderr, "q2_lds n=%d: %llu blocks; cycles per block: wait %.0f, tile+V %.0f, "
+            "mfma %.0f, store+publish %.0f\n", fp.n, h[4], h[0] / nbk, h[1] / nbk, h[2] / nbk,
+            h[3] / nbk);
+  }
 #endif
-      a.nlev2 = 0;  // bt_few_kernel: Q1 only
-      // Q1 with Z in LDS as well (single-level plans; TG_BT_Q1_LDS=0: bt_few's)
-      const char *q1l = getenv("TG_BT_Q1_LDS");  // development switch, read per call
-      // (n <= 4096: the workgroups of one XCD; larger n: one workgroup per CU
-      // of the device, placement-independent hand-offs)
-      const int W1 = cdiv(n, Q1R);
-      const bool q1l2 = W1 <= xq.cus_per_xcd && k <= 16;  // (column slabs: the other form)
-      const bool q1 = !(q1l && q1l[0] == '0') && a.single && a.nops > 0 &&
-                      (q1l2 || W1 <= xq.xcds * xq.cus_per_xcd);
-      if (!q1 && k > 32) return hipErrorInvalidValue;
-      if (q1) {
-        // partials in bt_few's sub-chunk partial area; arrivals in cnt[5]
-        // (column slabs: cnt[64 + 16 s]), the XCD election in cnt[24..27]
-        Q1LArgs la{Z, n, k, b.Y, b.T, dops, a.nops, a.part, q1l2 ? cnt + 5 : cnt + 64, cnt + 24,
-                   cnt + 1, W1, a.timeout, 0};
-        auto t1 = prof_begin(st, PROF_Q1, 0.0, 0.0);
-        // TG_BT_Q1_LDS=2 (tests): a grid of W1 only, spread over the XCDs, so
-        // the election comes up short and the bt_few fallback runs
-        if (q1l2) {
-          const int g1 = (q1l && q1l[0] == '2') ? W1 : W1 * xq.xcds;
-          hipLaunchKernelGGL(q1_lds_kernel<true>, dim3(g1), dim3(64 * Q1W), 0, st, la);
-          if ((e = hipGetLastError()) != hipSuccess) return e;
-        } else {
-          // slabs a launch: each its own arrival counter, partials reused by
-          // the next launch (stream order)
-          const int c1 = q1_conc(n, k);
-          for (la.slab0 = 0; la.slab0 < nslab; la.slab0 += c1) {
-            hipLaunchKernelGGL(q1_lds_kernel<false>, dim3(W1, std::min(c1, nslab - la.slab0)),
-                               dim3(64 * Q1W), 0, st, la);
-            if ((e = hipGetLastError()) != hipSuccess) return e;
-          }
-        }
-        prof_end(st, t1);
-        // did the workers land on one XCD?  (the sync is the one the
-        // all-LDS path makes anyway to read the timeout flag)
-        unsigned h[28];
-        e = hipMemcpyAsync(h, cnt, sizeof(h), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);  // also: ops read before they go
-        if (e != hipSuccess) return e;
-        *timed_out = h[1] != 0u;
-        if (*timed_out) return hipSuccess;
-#if TG_Q1L_STATS
-        {
-          unsigned long long q[8];
-          (void)hipMemcpyFromSymbol(q, HIP_SYMBOL(g_q1l_stats), sizeof(q));
-          const double ns = double(q[6] ? q[6] : 1);
-          fprintf(stderr, "q1_lds n=%d: %llu worker-steps; cycles per step: stage + partials %.0f, "
-                  "drain %.0f, exchange %.0f, P sum + M + update %.0f\n", n, q[6], q[0] / ns,
-                  q[1] / ns, q[2] / ns, q[3] / ns + q[4] / ns + q[5] / ns);
-          const unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-          (void)hipMemcpyToSymbol(HIP_SYMBOL(g_q1l_stats), z, sizeof(z));
-        }
-#endif
-        if (h[27] == 0u) return hipSuccess;  // done: Q2 and Q1 both ran with Z in LDS
-        // not placed: Z untouched, bt_few_kernel's Q1 below
-      }
+  return hipSuccess;
+}
+
+// q1_lds_kernel, then the flag words.  *done: Q1 ran (false: the XCD form's
+// workers did not land on one XCD and left Z untouched, or the wait timed out).
+static hipError_t few_q1_lds(hipStream_t st, double *Z, const FewPlan &fp, const SbBufs &b,
+                             const FewDev &d, bool *timed_out, bool *done) {
+  *done = false;
+  const bool one_xcd = fp.q1 == FewQ1::LdsXcd;
+  // partials in bt_few's sub-chunk partial area; arrivals in cnt[5]
+  // (column slabs: cnt[64 + 16 s]), the XCD election in cnt[24..27]
+  Q1LArgs la{Z, fp.n, fp.k, b.Y, b.T, d.ops, fp.nops, d.part, one_xcd ? d.cnt + 5 : d.cnt + 64,
+             d.cnt + 24, d.cnt + 1, fp.W1, d.timeout, 0};
+  hipError_t e;
+  auto t1 = prof_begin(st, PROF_Q1, 0.0, 0.0);
+  if (one_xcd) {
+    hipLaunchKernelGGL(q1_lds_kernel<true>, dim3(fp.G1), dim3(64 * Q1W), 0, st, la);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  } else {
+    // c1 slabs a launch: each its own arrival counter, partials reused by
+    // the next launch (stream order)
+    for (la.slab0 = 0; la.slab0 < fp.nslab; la.slab0 += fp.c1) {
+      hipLaunchKernelGGL(q1_lds_kernel<false>, dim3(fp.W1, std::min(fp.c1, fp.nslab - la.slab0)),
+                         dim3(64 * Q1W), 0, st, la);
+      if ((e = hipGetLastError()) != hipSuccess) return e;
     }
   }
-  // one wave per Q2 block of the widest level, one workgroup per TSQR chunk
-  int W = std::min(256, std::max(std::max(std::max(1, cdiv(a.smax, BW)), pl.ncmax), few_nsub(pl)));
-  // the workers (one CU each: BtShared fills the LDS) must all be resident:
-  // in the XCD form they are workgroups of one XCD, so at most its CUs
-  // (sub-chunks beyond W are taken in turn by the loops)
-  const XcdInfo xi = xcd_info();
-  if (TG_BT_XCD) W = std::min(W, xi.cus_per_xcd);
-  a.wexp = W;
-  if (a.nlev2 == 0 && a.nops == 0 && !a.q2_wave) {
-    // everything ran in the LDS-resident kernels: only the timeout flag to read
-    unsigned h2[2] = {0u, 0u};
-    e = hipMemcpyAsync(h2, cnt, sizeof(h2), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);  // also: ops read before it goes
-    *timed_out = h2[1] != 0u;
-    return e;
+  prof_end(st, t1);
+  // did the workers land on one XCD?  (the sync is the one the all-LDS path
+  // makes anyway to read the timeout flag)
+  unsigned h[28];
+  if ((e = few_flags(st, d, h, 28, timed_out)) != hipSuccess || *timed_out) return e;
+#if TG_Q1L_STATS
+  {
+    unsigned long long q[8];
+    (void)hipMemcpyFromSymbol(q, HIP_SYMBOL(g_q1l_stats), sizeof(q));
+    const double ns = double(q[6] ? q[6] : 1);
+    fprintf(stderr, "q1_lds n=%d: %llu worker-steps; cycles per step: stage + partials %.0f, "
+            "drain %.0f, exchange %.0f, P sum + M + update %.0f\n", fp.n, q[6], q[0] / ns,
+            q[1] / ns, q[2] / ns, q[3] / ns + q[4] / ns + q[5] / ns);
+    const unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_q1l_stats), z, sizeof(z));
   }
-  auto tok = prof_begin(st, a.nlev2 > 0 ? PROF_Q2 : PROF_Q1, 0.0, 0.0);
-  const int grid = TG_BT_XCD ? xi.xcds * W : W;  // XCD form: W land on each XCD
-  if (a.q2_wave) {
-    if (k <= 16)
-      hipLaunchKernelGGL((bt_few_kernel<1, true>), dim3(grid), dim3(64 * BW), 0, st, a);
-    else
-      hipLaunchKernelGGL((bt_few_kernel<2, true>), dim3(grid), dim3(64 * BW), 0, st, a);
+#endif
+  *done = h[27] == 0u;
+  return hipSuccess;
+}
+
+// bt_few_kernel: the nlev2 Q2 levels (0: Q1 only) and the Q1 steps.
+static hipError_t few_bt(hipStream_t st, double *Z, const FewPlan &fp, const SbPlan &pl,
+                         const SbBufs &b, const FewDev &d, int nlev2, bool *timed_out) {
+  const bool wave = fp.q2 == FewQ2::Wave;
+  hipError_t e;
+  if (wave && fp.ng2 > 0) {
+    e = hipMemsetAsync(d.colflag, 0, ((size_t(fp.ng2) * 4 + 15) & ~size_t(15)), st);
+    if (e != hipSuccess) return e;
+  }
+  const BtArgs a{Z, fp.n, fp.k, b.V2, b.T2, fp.smax, fp.ng2, nlev2, b.Y, b.T, d.ops, fp.nops,
+                 pl.single ? 1 : 0, d.part, d.cnt, d.timeout, fp.W, d.colflag, wave ? 1 : 0};
+  auto tok = prof_begin(st, nlev2 > 0 ? PROF_Q2 : PROF_Q1, 0.0, 0.0);
+  const dim3 grid(fp.grid), block(64 * BW);
+  if (wave) {
+    if (fp.k <= 16) hipLaunchKernelGGL((bt_few_kernel<1, true>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((bt_few_kernel<2, true>), grid, block, 0, st, a);
   } else {
-    if (k <= 16)
-      hipLaunchKernelGGL((bt_few_kernel<1, false>), dim3(grid), dim3(64 * BW), 0, st, a);
-    else
-      hipLaunchKernelGGL((bt_few_kernel<2, false>), dim3(grid), dim3(64 * BW), 0, st, a);
+    if (fp.k <= 16) hipLaunchKernelGGL((bt_few_kernel<1, false>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((bt_few_kernel<2, false>), grid, block, 0, st, a);
   }
   prof_end(st, tok);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   unsigned h[24] = {0};
-  e = hipMemcpyAsync(h, cnt, sizeof(h), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);  // also: ops read before it goes
-  *timed_out = h[1] != 0u;
+  e = few_flags(st, d, h, 24, timed_out);
 #ifdef TG_BT_STATS
   const unsigned long long *q = reinterpret_cast<const unsigned long long *>(h + 8);
   fprintf(stderr, "bt_few: W %u  Q2 work %.3f ms barrier %.3f ms (%d levels)  Q1 work %.3f ms "
-          "barrier %.3f ms (%d steps)\n", h[3], q[0] / 1e5, q[1] / 1e5, a.nlev2, q[2] / 1e5,
-          q[3] / 1e5, a.nops);
+          "barrier %.3f ms (%d steps)\n", h[3], q[0] / 1e5, q[1] / 1e5, nlev2, q[2] / 1e5,
+          q[3] / 1e5, fp.nops);
 #endif
   return e;
+}
+
+hipError_t sb_apply_few(hipStream_t st, double *Z, const FewPlan &fp, const SbPlan &pl,
+                        const SbBufs &b, void *dev, bool *timed_out) {
+  *timed_out = false;
+  if (!fp.ok) return hipErrorInvalidValue;
+  char *base = static_cast<char *>(dev);
+  const FewDev d{static_cast<unsigned *>(dev), reinterpret_cast<Q1Op *>(base + FEW_HDR),
+                 reinterpret_cast<double *>(base + fp.part_off),
+                 reinterpret_cast<unsigned *>(base + fp.flag_off),
+                 spin_timeout_ticks("TG_BT_TIMEOUT_TICKS")};
+  std::vector<Q1Op> ops;  // read by the upload until the sync of few_flags
+  hipError_t e = few_upload(st, pl, d, ops);
+  if (e != hipSuccess) return e;
+  int nlev2 = fp.nlev2;
+  if (fp.q2 == FewQ2::Lds) {
+    if ((e = few_q2_lds(st, Z, fp, b, d)) != hipSuccess) return e;
+    nlev2 = 0;  // bt_few_kernel: Q1 only
+  }
+  if (fp.q1 != FewQ1::InFew) {
+    bool done = false;  // done: Q2 and Q1 both ran with Z in LDS
+    e = few_q1_lds(st, Z, fp, b, d, timed_out, &done);
+    if (e != hipSuccess || *timed_out || done) return e;
+  }
+  if (nlev2 == 0 && fp.nops == 0 && fp.q2 != FewQ2::Wave) {
+    // everything ran in the LDS-resident kernels: only the timeout flag to read
+    unsigned h[2] = {0u, 0u};
+    return few_flags(st, d, h, 2, timed_out);
+  }
+  return few_bt(st, Z, fp, pl, b, d, nlev2, timed_out);
 }
 
 }  // namespace tg

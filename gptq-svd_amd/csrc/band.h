@@ -152,13 +152,49 @@ hipError_t sb_q2_tfactors(hipStream_t st, int n, const double *V2, double *T2);
 // side stream of the band reduction: fork after the work queued on st, join back into st
 hipError_t side_fork(hipStream_t st, hipStream_t *side);
 hipError_t side_join(hipStream_t st);
-// Z (n x k row-major) <- Q1 Q2 Z with Z resident on chip (backtr.hip): k <= 32,
-// or up to 128 in 16-column slabs when sb_apply_few_ok; T2 must hold the Q2 T
-// factors; dev: sb_apply_few_scratch bytes of device scratch.  Syncs the
-// stream (reads the barrier timeout flag).
-bool sb_apply_few_ok(const SbPlan &pl, int n, int k);
-size_t sb_apply_few_scratch(const SbPlan &pl, int n, int k);
-hipError_t sb_apply_few(hipStream_t st, int n, double *Z, int k, const SbPlan &pl,
+// A fork that every exit joins: join() where the side stream's work is needed
+// (reports the error), the destructor for a fork still open (discards it).
+struct SideFork {
+  hipStream_t st = nullptr;
+  bool open = false;
+  SideFork() = default;
+  SideFork(const SideFork &) = delete;
+  SideFork &operator=(const SideFork &) = delete;
+  ~SideFork() { (void)join(); }
+  hipError_t fork(hipStream_t s, hipStream_t *side) {
+    const hipError_t e = side_fork(s, side);
+    if (e == hipSuccess) st = s, open = true;
+    return e;
+  }
+  hipError_t join() {
+    if (!open) return hipSuccess;
+    open = false;
+    return side_join(st);
+  }
+};
+// What sb_apply_few will do for k columns (few_plan, backtr.hip: built once per
+// call, the one reader of the TG_BT_SLABS / Q2_WAVE / Q2_LDS / Q1_LDS switches).
+enum class FewQ2 { InFew, Wave, Lds };  // bt_few_kernel's levels, its wavefront, q2_lds_kernel
+enum class FewQ1 { InFew, LdsXcd, LdsDevice };  // bt_few_kernel, q1_lds_kernel<true>, <false>
+struct FewPlan {
+  bool ok = false;           // k <= 32, or up to 128 when both LDS-resident kernels run
+  int n = 0, k = 0;
+  bool slabs = false;        // 16-column slabs (k > 16)
+  int nslab = 1;
+  FewQ2 q2 = FewQ2::InFew;
+  int Wq = 0, c2 = 1;        // q2_lds_kernel: workgroups, slabs a launch
+  FewQ1 q1 = FewQ1::InFew;
+  int W1 = 0, c1 = 1, G1 = 0;  // q1_lds_kernel: workgroups, slabs a launch, grid of the XCD form
+  bool q1_short = false;     // TG_BT_Q1_LDS=2: G1 = W1, the election comes up short
+  int smax = 0, ng2 = 0, nlev2 = 0, nops = 0;  // Q2 blocks / groups / levels, Q1 steps
+  int W = 0, grid = 0;       // bt_few_kernel: workers wanted, grid
+  size_t part_off = 0, flag_off = 0, total = 0;  // scratch bytes: header, ops | partials | flags
+};
+FewPlan few_plan(const SbPlan &pl, int n, int k);
+// Z (n x k row-major) <- Q1 Q2 Z with Z resident on chip (backtr.hip), as
+// plan (ok) says; T2 must hold the Q2 T factors; dev: plan.total bytes of
+// device scratch.  Syncs the stream (reads the barrier timeout flag).
+hipError_t sb_apply_few(hipStream_t st, double *Z, const FewPlan &plan, const SbPlan &pl,
                         const SbBufs &b, void *dev, bool *timed_out);
 // Z (n x k row-major) <- Q1 Z.
 hipError_t sb_apply_q1(hipStream_t st, int n, double *Z, int k, const SbPlan &pl,

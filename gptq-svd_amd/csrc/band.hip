@@ -134,16 +134,6 @@ __device__ inline double rcp_nr(double x) {
   return fma(fma(-x, r, 1.0), r, r);
 }
 
-__device__ inline double wave_allsum(double s) {
-  s = hsum32(s);
-  s = hsum16(s);
-  s += xdpp<DPP_MIRROR>(s);
-  s += xdpp<DPP_HALF_MIRROR>(s);
-  s += xdpp<DPP_XOR3>(s);
-  s += xdpp<DPP_XOR1>(s);
-  return s;
-}
-
 // Reduce-scatter of the 32 products v * r[l] over the wave: lane ends with
 // the sum of column rs_col(lane) (bits 5..1 of the lane id pick the half kept
 // at each step).
@@ -200,37 +190,6 @@ __device__ inline double reduce_scatter32(const double (&r0)[32], const double (
     p[0] = (up ? p[1] : p[0]) + recv;
   }
   return p[0] + xdpp<DPP_XOR1>(p[0]);
-}
-
-// Uniform-index access to a register array: a switch on the (scalar) index
-// keeps every access static, so the array stays in VGPRs.
-#define TG_CASES32(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) \
-  X(13) X(14) X(15) X(16) X(17) X(18) X(19) X(20) X(21) X(22) X(23) X(24) X(25) X(26) X(27) \
-  X(28) X(29) X(30) X(31)
-__device__ inline void ugets(const double (&a)[32], const double (&b)[32], int j, double &x,
-                             double &y) {
-  switch (j) {
-#define TG_GET(k)  \
-  case k:          \
-    x = a[k];      \
-    y = b[k];      \
-    break;
-    TG_CASES32(TG_GET)
-#undef TG_GET
-    default: x = y = 0.0;
-  }
-}
-__device__ inline void usets(double (&a)[32], double (&b)[32], int j, double x, double y) {
-  switch (j) {
-#define TG_SET(k)  \
-  case k:          \
-    a[k] = x;      \
-    b[k] = y;      \
-    break;
-    TG_CASES32(TG_SET)
-#undef TG_SET
-    default: break;
-  }
 }
 
 // Householder QR of one leaf (chunk z of `m` rows, rows kb..ke of src, 32
@@ -734,8 +693,6 @@ struct XmArgs {
   double *xpart;
   unsigned *cbt;
 };
-// doubles of one block's partials: Y^T X, + the four pair products
-__host__ __device__ inline int xm_np(const XmArgs &g) { return g.Ya ? 5 : 1; }
 // The product is formed transposed, Xᵀ[:, j-block] = YTᵀ · A22[:, j-block]
 // (A22 symmetric): the MFMA B operand is then 4 rows x 16 consecutive
 // columns of A22, so lane l reads A22[k + l/16][j0 + l%16] and every load
@@ -1821,16 +1778,6 @@ hipError_t side_join(hipStream_t st) {
   return hipSuccess;
 }
 
-// One compact-WY block per panel (pqr.hip): panel QR, X = A22 YT, M, update.
-// (Measured and removed in round 3's clean-up, DESIGN.md §5: a look-ahead
-// with the next panel's QR on a side stream, +5 ms -- the QR's workgroups need
-// a whole CU's LDS and wait for the trailing update to drain; the same on
-// CU-masked streams, update kernels 1.3-2x slower; A22 kept as its lower
-// triangle, X 27 -> 35 us for syr2k 38 -> 35 us.  Round 5: the look-ahead
-// with the update's workgroups kept off the QR's XCD (b % 8 != 0, dense
-// tile index) does overlap the two, but the next panel's column update and
-// the cross-stream waits cost what the overlap saves: 59.11 vs 59.11 ms at
-// n = 4096, +2 ms at 12,288.)
 // X = A22 YT and M = T^T Y^T X in one launch (row blocks of A22)
 static int xm_nbc(int m) {
   const char *fx = getenv("TG_XM_NBC");  // development switch (1 | 2), read per call

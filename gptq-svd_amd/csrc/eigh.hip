@@ -1689,47 +1689,39 @@ extern "C" size_t tg_eigh_workspace_size(int n) {
   return s.off + 256;
 }
 
-extern "C" int tg_eigh_values(void *stream, double *A, int n, int lda, double *w_asc, void *ws,
-                              size_t ws_bytes) {
-  TG_ARG(A, 2, "null A");
-  TG_ARG(n >= 1, 3, "n < 1");
-  TG_ARG(lda >= n, 4, "lda < n");
-  TG_ARG(w_asc, 5, "null w");
-  hipStream_t st = (hipStream_t)stream;
-  tg::Arena ar(ws, ws_bytes);
-  Tri w{};
-  tri_layout(ar, n, &w);
-  tg::SbPlan pl(n);
-  tg::SbBufs sb{};
-  tg::sb_layout(ar, n, n, pl, &sb);
-  TG_WS(ar);
-  const bool ts = two_stage(n);
-  if (ts) {
-    TG_HIP(tg::sy2sb(st, A, lda, n, pl, sb));
-    TG_HIP(tg::sb2st(st, A, lda, n, sb.Bst, sb.V2, sb.prog, w.d, w.e));
-    bool stalled = false, broken = false;
-    TG_HIP(tg::sb2st_stalled(st, n, sb.prog, &stalled, &broken));
-    bool ptmo = false;
-    TG_HIP(tg::sy2sb_timed_out(st, pl, sb, &ptmo));
-    if (ptmo) {
-      tg::set_error("tg_eigh_values: panel-QR grid barrier timed out; the band form is invalid");
-      return int(hipErrorLaunchTimeOut);
-    }
-    if (stalled || broken)  // all-ones bytes: NaN eigenvalues for any caller that ignores the code
-      TG_HIP(hipMemsetAsync(w_asc, 0xff, sizeof(double) * size_t(n), st));
-    if (stalled) {
-      tg::set_error("tg_eigh_values: bulge-chasing pipeline stalled (a hand-off wait timed out); "
-                    "the tridiagonal form is invalid");
-      return int(hipErrorLaunchTimeOut);
-    }
-    if (broken) {
-      tg::set_error("tg_eigh_values: the tridiagonal failed its invariant check (trace / "
-                    "Frobenius norm of the band not preserved by the bulge chase); the "
-                    "eigenvalues are poisoned");
-      return int(hipErrorIllegalState);
-    }
+// Stages of tg_eigh_values (tg_eigh_vectors_range's: further down).  Each queues
+// its work on st in order and returns the ABI's int (0, or what TG_HIP reported).
+// sy2sb and sb2st, then the read-backs of their three failure flags.
+static int reduce_two_stage(hipStream_t st, double *A, int lda, int n, const tg::SbPlan &pl,
+                            const tg::SbBufs &sb, const Tri &w, double *w_asc) {
+  TG_HIP(tg::sy2sb(st, A, lda, n, pl, sb));
+  TG_HIP(tg::sb2st(st, A, lda, n, sb.Bst, sb.V2, sb.prog, w.d, w.e));
+  bool stalled = false, broken = false;
+  TG_HIP(tg::sb2st_stalled(st, n, sb.prog, &stalled, &broken));
+  bool ptmo = false;
+  TG_HIP(tg::sy2sb_timed_out(st, pl, sb, &ptmo));
+  if (ptmo) {
+    tg::set_error("tg_eigh_values: panel-QR grid barrier timed out; the band form is invalid");
+    return int(hipErrorLaunchTimeOut);
   }
-  if (!ts) {
+  if (stalled || broken)  // all-ones bytes: NaN eigenvalues for any caller that ignores the code
+    TG_HIP(hipMemsetAsync(w_asc, 0xff, sizeof(double) * size_t(n), st));
+  if (stalled) {
+    tg::set_error("tg_eigh_values: bulge-chasing pipeline stalled (a hand-off wait timed out); "
+                  "the tridiagonal form is invalid");
+    return int(hipErrorLaunchTimeOut);
+  }
+  if (broken) {
+    tg::set_error("tg_eigh_values: the tridiagonal failed its invariant check (trace / "
+                  "Frobenius norm of the band not preserved by the bulge chase); the "
+                  "eigenvalues are poisoned");
+    return int(hipErrorIllegalState);
+  }
+  return 0;
+}
+
+// One-stage reduction: dlatrd panels of NB columns and their rank-2NB updates.
+static int reduce_one_stage(hipStream_t st, double *A, int lda, int n, const Tri &w) {
   TG_HIP(hipMemsetAsync(w.V, 0, sizeof(double) * size_t(n) * n, st));
   TG_HIP(hipMemsetAsync(w.cnt, 0, 16 * sizeof(unsigned), st));
   TG_HIP(hipMemsetAsync(w.e, 0, sizeof(double) * n, st));
@@ -1773,8 +1765,11 @@ extern "C" int tg_eigh_values(void *stream, double *A, int n, int lda, double *w
       tg::prof_end(st, tok);
     }
   }
-  }  // one-stage
-  // eigenvalues of T
+  return 0;
+}
+
+// Eigenvalues of T (w.d, w.e) into w_asc: bounds, split, grid count, bisection, sort.
+static int tridiag_values(hipStream_t st, int n, const Tri &w, double *w_asc) {
   double *bnd = w.scal;
   hipLaunchKernelGGL(tri_bounds_kernel, dim3(1), dim3(256), 0, st, w.d, w.e, n, bnd);
   TG_LAUNCHED();
@@ -1825,6 +1820,26 @@ extern "C" int tg_eigh_values(void *stream, double *A, int n, int lda, double *w
   return 0;
 }
 
+extern "C" int tg_eigh_values(void *stream, double *A, int n, int lda, double *w_asc, void *ws,
+                              size_t ws_bytes) {
+  TG_ARG(A, 2, "null A");
+  TG_ARG(n >= 1, 3, "n < 1");
+  TG_ARG(lda >= n, 4, "lda < n");
+  TG_ARG(w_asc, 5, "null w");
+  hipStream_t st = (hipStream_t)stream;
+  tg::Arena ar(ws, ws_bytes);
+  Tri w{};
+  tri_layout(ar, n, &w);
+  tg::SbPlan pl(n);
+  tg::SbBufs sb{};
+  tg::sb_layout(ar, n, n, pl, &sb);
+  TG_WS(ar);
+  if (int rc = two_stage(n) ? reduce_two_stage(st, A, lda, n, pl, sb, w, w_asc)
+                            : reduce_one_stage(st, A, lda, n, w))
+    return rc;
+  return tridiag_values(st, n, w, w_asc);
+}
+
 extern "C" int tg_truncation_rank(void *stream, const double *w_asc, int n, double threshold,
                                   int rule, double *S_desc, int32_t *k_dev) {
   TG_ARG(w_asc, 2, "null w");
@@ -1847,47 +1862,10 @@ extern "C" int tg_truncation_rank(void *stream, const double *w_asc, int n, doub
   return 0;
 }
 
-extern "C" int tg_eigh_vectors(void *stream, int n, const double *w_asc, int k, double *Vh, int ldv,
-                               void *ws, size_t ws_bytes) {
-  TG_ARG(n >= 1, 2, "n < 1");
-  TG_ARG(w_asc, 3, "null w");
-  TG_ARG(k >= 1 && k <= n, 4, "k must be in [1, n]");
-  TG_ARG(Vh, 5, "null Vh");
-  TG_ARG(ldv >= n, 6, "ldv < n");
-  return tg_eigh_vectors_range(stream, n, w_asc, 0, k, Vh, ldv, ws, ws_bytes);
-}
-
-extern "C" int tg_eigh_vectors_range(void *stream, int n, const double *w_asc, int first, int k,
-                                     double *Vh, int ldv, void *ws, size_t ws_bytes) {
-  TG_ARG(n >= 1, 2, "n < 1");
-  TG_ARG(w_asc, 3, "null w");
-  TG_ARG(first >= 0 && first < n, 4, "first must be in [0, n)");
-  TG_ARG(k >= 1 && first + k <= n, 5, "count must be in [1, n - first]");
-  TG_ARG(Vh, 6, "null Vh");
-  TG_ARG(ldv >= n, 7, "ldv < n");
-  hipStream_t st = (hipStream_t)stream;
-  tg::Arena ar(ws, ws_bytes);
-  Tri w{};
-  tri_layout(ar, n, &w);
-  tg::SbPlan pl(n);
-  tg::SbBufs sb{};
-  tg::sb_layout(ar, n, n, pl, &sb);
-  TG_WS(ar);
+// Inverse iteration for eigenvalues [first, first + k) of T into w.Z (n x k).
+static int inverse_iteration(hipStream_t st, int n, const double *w_asc, int first, int k,
+                             const Tri &w) {
   const double *bnd = w.scal;
-  // the few-vector back-transform's Q2 T factors depend only on the bulge
-  // reflectors: formed on the side stream beside inverse iteration (14
-  // one-wave workgroups) and the cluster checks, joined before the apply
-  const bool ts = two_stage(n);
-  const bool multi = getenv("TG_BT_MULTI") != nullptr;  // read per call (tests set it)
-  const bool few = ts && !multi && tg::sb_apply_few_ok(pl, n, k) &&
-                   tg::sb_apply_few_scratch(pl, n, k) <= sizeof(double) * size_t(n) * tg::SB_B;
-  const char *tfs = getenv("TG_BT_TF_SIDE");  // development switch: 0 = in order, per call
-  const bool tf_side = few && !(tfs && tfs[0] == '0');
-  if (tf_side) {
-    hipStream_t side = nullptr;
-    TG_HIP(tg::side_fork(st, &side));
-    TG_HIP(tg::sb_q2_tfactors(side, n, sb.V2, sb.T2));
-  }
   auto itok = tg::prof_begin(st, tg::PROF_INVIT, 8.0 * 5 * 4 * double(n) * k, 0.0);
   const char *ie = getenv("TG_INVIT_ITERS");
   const int iters = ie ? std::max(1, std::min(5, atoi(ie))) : 2;
@@ -1929,114 +1907,177 @@ extern "C" int tg_eigh_vectors_range(void *stream, int n, const double *w_asc, i
     fprintf(stderr, "\n");
   }
 #endif
-  {
-    const char *ot = getenv("TG_INVIT_ORTOL");
-    const double ortol = ot ? atof(ot) : 1e-6;
-    // panel path: X (p x pw) + Gram partials + Rinv + flag in w.lu (3 n^2 doubles)
-    const int cq_np = std::max(1, std::min(64, n / 256));
-    const size_t cq_need = size_t(k) * MGS_MAX + size_t(cq_np + 1) * MGS_MAX * MGS_MAX + 1;
-    const bool cq = cq_need <= 3 * size_t(n) * n && !getenv("TG_ORTH_MGS");  // (tests set it)
-    hipLaunchKernelGGL(cluster_scan_kernel, dim3(1), dim3(64), 0, st, w_asc, n, k, first, bnd,
-                       ortol, cq ? MGS_SMALL : MGS_MAX, w.cl);
+  return 0;
+}
+
+// Clusters of close eigenvalues: MGS in the small ones, CholQR / MGS panels in the big.
+static int reorthogonalise_clusters(hipStream_t st, int n, const double *w_asc, int first, int k,
+                                    const Tri &w) {
+  const double *bnd = w.scal;
+  const char *ot = getenv("TG_INVIT_ORTOL");
+  const double ortol = ot ? atof(ot) : 1e-6;
+  // panel path: X (p x pw) + Gram partials + Rinv + flag in w.lu (3 n^2 doubles)
+  const int cq_np = std::max(1, std::min(64, n / 256));
+  const size_t cq_need = size_t(k) * MGS_MAX + size_t(cq_np + 1) * MGS_MAX * MGS_MAX + 1;
+  const bool cq = cq_need <= 3 * size_t(n) * n && !getenv("TG_ORTH_MGS");  // (tests set it)
+  hipLaunchKernelGGL(cluster_scan_kernel, dim3(1), dim3(64), 0, st, w_asc, n, k, first, bnd,
+                     ortol, cq ? MGS_SMALL : MGS_MAX, w.cl);
+  TG_LAUNCHED();
+  int32_t cnt[2] = {0, 0};
+  TG_HIP(hipMemcpyAsync(cnt, w.cl, sizeof(cnt), hipMemcpyDeviceToHost, st));
+  TG_HIP(hipStreamSynchronize(st));
+  if (cnt[0] > 0) {
+    hipLaunchKernelGGL(mgs_cols_kernel, dim3(cnt[0]), dim3(256), 0, st, w.cl + 2, n, k, w.Z,
+                       nullptr);
     TG_LAUNCHED();
-    int32_t cnt[2] = {0, 0};
-    TG_HIP(hipMemcpyAsync(cnt, w.cl, sizeof(cnt), hipMemcpyDeviceToHost, st));
+  }
+  if (cnt[1] > 0) {
+    std::vector<int32_t> big(2 * size_t(cnt[1]));
+    TG_HIP(hipMemcpyAsync(big.data(), w.cl + 2 + 2 * size_t(n), sizeof(int32_t) * big.size(),
+                          hipMemcpyDeviceToHost, st));
     TG_HIP(hipStreamSynchronize(st));
-    if (cnt[0] > 0) {
-      hipLaunchKernelGGL(mgs_cols_kernel, dim3(cnt[0]), dim3(256), 0, st, w.cl + 2, n, k, w.Z,
-                         nullptr);
-      TG_LAUNCHED();
-    }
-    if (cnt[1] > 0) {
-      std::vector<int32_t> big(2 * size_t(cnt[1]));
-      TG_HIP(hipMemcpyAsync(big.data(), w.cl + 2 + 2 * size_t(n), sizeof(int32_t) * big.size(),
-                            hipMemcpyDeviceToHost, st));
-      TG_HIP(hipStreamSynchronize(st));
-      // panel entries (start, width) of every big cluster, for mgs_cols_kernel
-      std::vector<int32_t> pan;
-      for (int c = 0; c < cnt[1]; ++c)
-        for (int p = 0; p < big[2 * c + 1]; p += MGS_MAX) {
-          pan.push_back(big[2 * c] + p);
-          pan.push_back(std::min(MGS_MAX, big[2 * c + 1] - p));
-        }
-      int32_t *plist = w.cl + 2 + 2 * size_t(n) + 2 * size_t(cnt[1]);
-      TG_HIP(hipMemcpyAsync(plist, pan.data(), sizeof(int32_t) * pan.size(),
-                            hipMemcpyHostToDevice, st));
-      double *X = w.lu;  // (cluster columns done) x MGS_MAX scratch
-      double *part = X + size_t(k) * MGS_MAX;
-      double *Rinv = part + size_t(cq_np) * MGS_MAX * MGS_MAX;
-      int *bad = reinterpret_cast<int *>(Rinv + MGS_MAX * MGS_MAX);
-      const int rows_per = tg::cdiv(tg::cdiv(n, cq_np), CQ_ROWS) * CQ_ROWS;
-      const int np = tg::cdiv(n, rows_per);
-      int e = 0;
-      for (int c = 0; c < cnt[1]; ++c) {
-        const int cs = big[2 * c], cl = big[2 * c + 1];
-        for (int p = 0; p < cl; p += MGS_MAX, ++e) {
-          const int pw = std::min(MGS_MAX, cl - p), p0 = cs + p;
-          for (int pass = 0; pass < 2 && p > 0; ++pass) {
-            // Z_p -= Z_done (Z_done^T Z_p)
-            TG_HIP(tg::dgemm(st, true, false, p, pw, n, 1.0, w.Z + cs, k, w.Z + p0, k, 0.0, X, pw));
-            TG_HIP(tg::dgemm(st, false, false, n, pw, p, -1.0, w.Z + cs, k, X, pw, 1.0, w.Z + p0,
-                             k));
-          }
-          if (cq) {
-            TG_HIP(hipMemsetAsync(bad, 0, sizeof(int), st));
-            for (int round = 0; round < 2; ++round) {
-              hipLaunchKernelGGL(cq_gram_kernel, dim3(np), dim3(256), 0, st, w.Z, n, k, p0, pw,
-                                 rows_per, bad, part);
-              hipLaunchKernelGGL(cq_chol_kernel, dim3(1), dim3(256), 0, st, part, np, pw, Rinv, bad);
-              hipLaunchKernelGGL(cq_apply_kernel, dim3(tg::cdiv(n, 256)), dim3(256), 0, st, w.Z, n,
-                                 k, p0, pw, Rinv, bad);
-            }
-          }
-          hipLaunchKernelGGL(mgs_cols_kernel, dim3(1), dim3(256), 0, st, plist + 2 * e, n, k, w.Z,
-                             cq ? bad : nullptr);
-          TG_LAUNCHED();
-        }
+    // panel entries (start, width) of every big cluster, for mgs_cols_kernel
+    std::vector<int32_t> pan;
+    for (int c = 0; c < cnt[1]; ++c)
+      for (int p = 0; p < big[2 * c + 1]; p += MGS_MAX) {
+        pan.push_back(big[2 * c] + p);
+        pan.push_back(std::min(MGS_MAX, big[2 * c + 1] - p));
       }
-      TG_HIP(hipStreamSynchronize(st));  // pan is read by the copy above
-    }
-  }
-  // back-transformation Z <- Q Z, Q = H_0 H_1 ... H_{n-2}
-  const int nref = ts ? 0 : n - 1;
-  if (ts) {
-    // few vectors (the complement path's request): the LDS-resident kernels
-    if (few) {
-      if (tf_side)
-        TG_HIP(tg::side_join(st));  // the T factors
-      else
-        TG_HIP(tg::sb_q2_tfactors(st, n, sb.V2, sb.T2));
-      bool tmo = false;
-      TG_HIP(tg::sb_apply_few(st, n, w.Z, k, pl, sb, sb.X, &tmo));
-      if (tmo) {
-        tg::set_error("tg_eigh_vectors_range: back-transformation grid barrier timed out");
-        return int(hipErrorLaunchTimeOut);
+    int32_t *plist = w.cl + 2 + 2 * size_t(n) + 2 * size_t(cnt[1]);
+    TG_HIP(hipMemcpyAsync(plist, pan.data(), sizeof(int32_t) * pan.size(),
+                          hipMemcpyHostToDevice, st));
+    double *X = w.lu;  // (cluster columns done) x MGS_MAX scratch
+    double *part = X + size_t(k) * MGS_MAX;
+    double *Rinv = part + size_t(cq_np) * MGS_MAX * MGS_MAX;
+    int *bad = reinterpret_cast<int *>(Rinv + MGS_MAX * MGS_MAX);
+    const int rows_per = tg::cdiv(tg::cdiv(n, cq_np), CQ_ROWS) * CQ_ROWS;
+    const int np = tg::cdiv(n, rows_per);
+    int e = 0;
+    for (int c = 0; c < cnt[1]; ++c) {
+      const int cs = big[2 * c], cl = big[2 * c + 1];
+      for (int p = 0; p < cl; p += MGS_MAX, ++e) {
+        const int pw = std::min(MGS_MAX, cl - p), p0 = cs + p;
+        for (int pass = 0; pass < 2 && p > 0; ++pass) {
+          // Z_p -= Z_done (Z_done^T Z_p)
+          TG_HIP(tg::dgemm(st, true, false, p, pw, n, 1.0, w.Z + cs, k, w.Z + p0, k, 0.0, X, pw));
+          TG_HIP(tg::dgemm(st, false, false, n, pw, p, -1.0, w.Z + cs, k, X, pw, 1.0, w.Z + p0,
+                           k));
+        }
+        if (cq) {
+          TG_HIP(hipMemsetAsync(bad, 0, sizeof(int), st));
+          for (int round = 0; round < 2; ++round) {
+            hipLaunchKernelGGL(cq_gram_kernel, dim3(np), dim3(256), 0, st, w.Z, n, k, p0, pw,
+                               rows_per, bad, part);
+            hipLaunchKernelGGL(cq_chol_kernel, dim3(1), dim3(256), 0, st, part, np, pw, Rinv, bad);
+            hipLaunchKernelGGL(cq_apply_kernel, dim3(tg::cdiv(n, 256)), dim3(256), 0, st, w.Z, n,
+                               k, p0, pw, Rinv, bad);
+          }
+        }
+        hipLaunchKernelGGL(mgs_cols_kernel, dim3(1), dim3(256), 0, st, plist + 2 * e, n, k, w.Z,
+                           cq ? bad : nullptr);
+        TG_LAUNCHED();
       }
-    } else {
-      TG_HIP(tg::sb_apply_q2(st, n, w.Z, k, sb.V2, sb.T2));
-      TG_HIP(tg::sb_apply_q1(st, n, w.Z, k, pl, sb));
     }
+    TG_HIP(hipStreamSynchronize(st));  // pan is read by the copy above
   }
-  if (nref > 0) {
-    const int nblk = tg::cdiv(nref, BT);
-    hipLaunchKernelGGL(tfactor_kernel, dim3(nblk), dim3(256), 0, st, w.V, n, nref, w.tau, w.Tf);
-    TG_LAUNCHED();
-    auto btok2 = tg::prof_begin(st, tg::PROF_BACKTR, 0.0, 2.0 * double(n) * n * k);
-    for (int b = nblk - 1; b >= 0; --b) {
-      const int p = b * BT, bw = min(BT, nref - p), r0 = p + 1;
-      const double *Vb = w.V + size_t(r0) * n + p;
-      // X1 = Vb^T Z[r0:, :]   (bw x k)
-      TG_HIP(tg::dgemm_splitk(st, true, false, bw, k, n - r0, 1.0, Vb, n, w.Z + size_t(r0) * k, k,
-                              0.0, w.X1, k, SPLITK, w.skp));
-      // X2 = T_b X1
-      TG_HIP(tg::dgemm(st, false, false, bw, k, bw, 1.0, w.Tf + size_t(b) * BT * BT, BT, w.X1, k,
-                       0.0, w.X2, k));
-      // Z[r0:, :] -= Vb X2
-      TG_HIP(tg::dgemm(st, false, false, n - r0, k, bw, -1.0, Vb, n, w.X2, k, 1.0,
-                       w.Z + size_t(r0) * k, k));
-    }
-    tg::prof_end(st, btok2);
+  return 0;
+}
+
+// Z <- Q1 Q2 Z.  few (the complement path's request): the LDS-resident kernels,
+// their Q2 T factors from the side stream if tf forked them.
+static int back_transform_two_stage(hipStream_t st, int n, int k, const Tri &w,
+                                    const tg::SbPlan &pl, const tg::SbBufs &sb,
+                                    const tg::FewPlan *few, tg::SideFork &tf) {
+  if (!few) {
+    TG_HIP(tg::sb_apply_q2(st, n, w.Z, k, sb.V2, sb.T2));
+    TG_HIP(tg::sb_apply_q1(st, n, w.Z, k, pl, sb));
+    return 0;
   }
+  if (tf.open)
+    TG_HIP(tf.join());  // the T factors
+  else
+    TG_HIP(tg::sb_q2_tfactors(st, n, sb.V2, sb.T2));
+  bool tmo = false;
+  TG_HIP(tg::sb_apply_few(st, w.Z, *few, pl, sb, sb.X, &tmo));
+  if (tmo) {
+    tg::set_error("tg_eigh_vectors_range: back-transformation grid barrier timed out");
+    return int(hipErrorLaunchTimeOut);
+  }
+  return 0;
+}
+
+// Z <- Q Z, Q = H_0 H_1 ... H_{n-2} in compact-WY blocks of BT reflectors.
+static int back_transform_one_stage(hipStream_t st, int n, int k, const Tri &w) {
+  const int nref = n - 1;
+  if (nref <= 0) return 0;
+  const int nblk = tg::cdiv(nref, BT);
+  hipLaunchKernelGGL(tfactor_kernel, dim3(nblk), dim3(256), 0, st, w.V, n, nref, w.tau, w.Tf);
+  TG_LAUNCHED();
+  auto btok2 = tg::prof_begin(st, tg::PROF_BACKTR, 0.0, 2.0 * double(n) * n * k);
+  for (int b = nblk - 1; b >= 0; --b) {
+    const int p = b * BT, bw = min(BT, nref - p), r0 = p + 1;
+    const double *Vb = w.V + size_t(r0) * n + p;
+    // X1 = Vb^T Z[r0:, :]   (bw x k)
+    TG_HIP(tg::dgemm_splitk(st, true, false, bw, k, n - r0, 1.0, Vb, n, w.Z + size_t(r0) * k, k,
+                            0.0, w.X1, k, SPLITK, w.skp));
+    // X2 = T_b X1
+    TG_HIP(tg::dgemm(st, false, false, bw, k, bw, 1.0, w.Tf + size_t(b) * BT * BT, BT, w.X1, k,
+                     0.0, w.X2, k));
+    // Z[r0:, :] -= Vb X2
+    TG_HIP(tg::dgemm(st, false, false, n - r0, k, bw, -1.0, Vb, n, w.X2, k, 1.0,
+                     w.Z + size_t(r0) * k, k));
+  }
+  tg::prof_end(st, btok2);
+  return 0;
+}
+
+extern "C" int tg_eigh_vectors(void *stream, int n, const double *w_asc, int k, double *Vh, int ldv,
+                               void *ws, size_t ws_bytes) {
+  TG_ARG(n >= 1, 2, "n < 1");
+  TG_ARG(w_asc, 3, "null w");
+  TG_ARG(k >= 1 && k <= n, 4, "k must be in [1, n]");
+  TG_ARG(Vh, 5, "null Vh");
+  TG_ARG(ldv >= n, 6, "ldv < n");
+  return tg_eigh_vectors_range(stream, n, w_asc, 0, k, Vh, ldv, ws, ws_bytes);
+}
+
+extern "C" int tg_eigh_vectors_range(void *stream, int n, const double *w_asc, int first, int k,
+                                     double *Vh, int ldv, void *ws, size_t ws_bytes) {
+  TG_ARG(n >= 1, 2, "n < 1");
+  TG_ARG(w_asc, 3, "null w");
+  TG_ARG(first >= 0 && first < n, 4, "first must be in [0, n)");
+  TG_ARG(k >= 1 && first + k <= n, 5, "count must be in [1, n - first]");
+  TG_ARG(Vh, 6, "null Vh");
+  TG_ARG(ldv >= n, 7, "ldv < n");
+  hipStream_t st = (hipStream_t)stream;
+  tg::Arena ar(ws, ws_bytes);
+  Tri w{};
+  tri_layout(ar, n, &w);
+  tg::SbPlan pl(n);
+  tg::SbBufs sb{};
+  tg::sb_layout(ar, n, n, pl, &sb);
+  TG_WS(ar);
+  // the few-vector back-transform (scratch: sb.X) and its Q2 T factors, which
+  // depend only on the bulge reflectors: formed on the side stream beside
+  // inverse iteration (14 one-wave workgroups) and the cluster checks, joined
+  // before the apply -- or by tf on any earlier exit
+  const bool ts = two_stage(n);
+  const bool multi = getenv("TG_BT_MULTI") != nullptr;  // read per call (tests set it)
+  const tg::FewPlan fp = ts && !multi ? tg::few_plan(pl, n, k) : tg::FewPlan{};
+  const bool fits = fp.total <= sizeof(double) * size_t(n) * tg::SB_B;
+  const tg::FewPlan *few = fp.ok && fits ? &fp : nullptr;
+  const char *tfs = getenv("TG_BT_TF_SIDE");  // development switch: 0 = in order, per call
+  tg::SideFork tf;
+  if (few && !(tfs && tfs[0] == '0')) {
+    hipStream_t side = nullptr;
+    TG_HIP(tf.fork(st, &side));
+    TG_HIP(tg::sb_q2_tfactors(side, n, sb.V2, sb.T2));
+  }
+  if (int rc = inverse_iteration(st, n, w_asc, first, k, w)) return rc;
+  if (int rc = reorthogonalise_clusters(st, n, w_asc, first, k, w)) return rc;
+  if (int rc = ts ? back_transform_two_stage(st, n, k, w, pl, sb, few, tf)
+                  : back_transform_one_stage(st, n, k, w))
+    return rc;
   hipLaunchKernelGGL(transpose_kernel, dim3(tg::cdiv(k, 32), tg::cdiv(n, 32)), dim3(32, 8), 0, st,
                      w.Z, n, k, Vh, ldv);
   TG_LAUNCHED();

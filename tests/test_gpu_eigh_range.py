@@ -457,3 +457,36 @@ def test_few_slabs(n, count, monkeypatch):
     if count <= 32:
         monkeypatch.setenv("TG_BT_SLABS", "0")
         assert np.abs(vectors(first, count) - Vh).max() <= 1e-12
+
+
+@pytest.mark.parametrize("n,count", [(1000, 40), (2048, 128)])
+def test_wide_few_switches_fall_back(n, count, monkeypatch):
+    """More than 32 vectors take the few-vector back-transform only while both
+    LDS-resident kernels run (csrc/backtr.hip few_plan).  A switch that removes
+    one of them (TG_BT_Q1_LDS=0, TG_BT_Q2_LDS=0, TG_BT_Q2_WAVE=1) selects the
+    level-by-level sb_apply_q2 / sb_apply_q1, as TG_BT_MULTI=1 does: the call
+    returns 0 and the vectors equal TG_BT_MULTI=1's bit for bit (the same
+    kernels after the same inverse iteration).  n = 1000, 40: three slabs, a
+    partial last one, a partial last sub-chunk; n = 2048, 128: eight slabs, Q1
+    in launches of three."""
+    from gptq_svd_amd import _lib as lib
+    Hd = torch.from_numpy(_wishart(n, 59)).to(DEV)
+    ws = lib.workspace(lib.lib.tg_eigh_workspace_size(n), torch.device(DEV))
+    w = torch.empty(n, dtype=torch.float64, device=DEV)
+    lib.call("tg_eigh_values", lib.stream(), lib.ptr(Hd), n, n, lib.ptr(w), lib.ptr(ws), ws.numel())
+    switches = ("TG_BT_MULTI", "TG_BT_Q1_LDS", "TG_BT_Q2_LDS", "TG_BT_Q2_WAVE")
+
+    def vectors(name, value):
+        for s in switches:
+            monkeypatch.delenv(s, raising=False)
+        monkeypatch.setenv(name, value)
+        V = torch.empty((count, n), dtype=torch.float64, device=DEV)
+        rc = lib.lib.tg_eigh_vectors_range(lib.stream(), n, lib.ptr(w), n - count, count,
+                                           lib.ptr(V), n, lib.ptr(ws), ws.numel())
+        assert rc == 0, (name, value, rc, lib.last_error())
+        torch.cuda.synchronize()
+        return V.cpu().numpy()
+
+    ref = vectors("TG_BT_MULTI", "1")
+    for name, value in (("TG_BT_Q1_LDS", "0"), ("TG_BT_Q2_LDS", "0"), ("TG_BT_Q2_WAVE", "1")):
+        assert np.array_equal(vectors(name, value), ref), name
