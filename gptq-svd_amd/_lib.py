@@ -105,6 +105,8 @@ _SIGS = {
     "tg_lr_down": ([_vp, _vp, _i, _i, _i64, _vp, _i, _i, _i, _i64, _vp, _i64, _vp, _sz], _i),
     "tg_lr_finish": ([_vp, _vp, _i64, _vp, _i64, _vp, _i, _i64, _i, _i, _i, _vp, _i, _vp, _i,
                       _i64], _i),
+    "tg_hadamard": ([_vp, _vp, _i, _i64, _i, _i64, _i, _vp, _i, _vp, _i, _i64], _i),
+    "tg_hadamard_sym": ([_vp, _vp, _i, _i64, _i, _vp], _i),
 }
 
 EXPORTED = []

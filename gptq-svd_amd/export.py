@@ -31,6 +31,14 @@ its effective weight being W + lr_a lr_b, and ``quantize_config.json`` records
 Loaders that do not know the two tensors (AutoGPTQ, GPTQModel) cannot apply
 the correction.
 
+Hadamard rotation (``quantize_model(rotate=...)``): a rotated linear also has
+  ``<name>.had_sign`` int32 (in/32,), bit j of word i = input column 32 i + j is
+  negated, and ``quantize_config.json`` records ``"rotation": {"kind":
+  "hadamard", "blocks": {name: block}}``.  Its packed weight (and ``lr_b``) is
+  that of the rotated basis W Q, so a consumer must apply x -> x Q to the
+  layer's input.  Checkpoints without the key are read exactly
+  as before.
+
 ``load_quantized`` is the way back: it puts the packed tensors into
 ``qlinear.QuantLinear`` (``qlinear.MXQuantLinear`` for MXFP4) modules of a
 model, which run them without unpacking.
@@ -67,7 +75,15 @@ def save_quantized(path: str, model: torch.nn.Module, packed: Dict[str, Dict[str
     sd = model.state_dict()
     tensors: Dict[str, torch.Tensor] = {}
     lowrank = 0
+    blocks: Dict[str, int] = {}
     for name, t in packed.items():
+        if (t.get("had_sign") is None) != (not t.get("had_block")):
+            raise ValueError(f"{name}: had_sign and had_block come together")
+        if t.get("had_sign") is not None:
+            if t["had_sign"].dtype != torch.int32:
+                raise ValueError(f"{name}: had_sign must be int32, got {t['had_sign'].dtype}")
+            tensors[f"{name}.had_sign"] = t["had_sign"].contiguous().cpu()
+            blocks[name] = int(t["had_block"])
         if (t.get("lr_a") is None) != (t.get("lr_b") is None):
             raise ValueError(f"{name}: lr_a and lr_b come together")
         if t.get("lr_a") is not None:
@@ -108,6 +124,8 @@ def save_quantized(path: str, model: torch.nn.Module, packed: Dict[str, Dict[str
         qc.update(sym=True, checkpoint_format="mxfp4", scale_dtype="e8m0")
     if lowrank:
         qc["lowrank"] = lowrank
+    if blocks:
+        qc["rotation"] = {"kind": "hadamard", "blocks": blocks}
     if extra_config:
         qc["truncgptq"] = extra_config
     with open(os.path.join(path, "quantize_config.json"), "w") as f:
@@ -137,6 +155,31 @@ def _lowrank_of(tensors: Dict[str, torch.Tensor], name: str, keys: Dict[str, str
     return None if a is None else (a, b)
 
 
+def _rotation_blocks(qc: Dict[str, Any], tensors: Dict[str, torch.Tensor]) -> Dict[str, int]:
+    """{name: block} of the checkpoint's "rotation" entry ({} without one),
+    checked against the ``had_sign`` tensors it holds."""
+    rot = qc.get("rotation")
+    if rot is None:
+        blocks = {}
+    elif not isinstance(rot, dict) or rot.get("kind") != "hadamard" \
+            or not isinstance(rot.get("blocks"), dict):
+        raise ValueError(f"quantize_config.json: unsupported rotation entry {rot!r}")
+    else:
+        blocks = {k: int(v) for k, v in rot["blocks"].items()}
+    signed = {k[:-len(".had_sign")] for k in tensors if k.endswith(".had_sign")}
+    if signed != set(blocks):
+        raise KeyError(f"quantize_config.json's rotation blocks and the had_sign tensors "
+                       f"disagree: {sorted(signed ^ set(blocks))}")
+    return blocks
+
+
+def _rotation_of(tensors: Dict[str, torch.Tensor], name: str, blocks: Dict[str, int],
+                 keys: Dict[str, str]):
+    """The (block, sign_bits) pair of a linear, or None; `keys` gains the tensor's name."""
+    keys.update(had_sign=f"{name}.had_sign")
+    return (blocks[name], tensors[keys["had_sign"]]) if name in blocks else None
+
+
 def _set_submodule(model: torch.nn.Module, name: str, new: torch.nn.Module) -> None:
     parent_name, _, leaf = name.rpartition(".")
     parent = model.get_submodule(parent_name) if parent_name else model
@@ -150,7 +193,9 @@ def load_quantized(model: torch.nn.Module, path: str, device=None,
     ``<name>.qweight`` is in the checkpoint becomes a ``qlinear.QuantLinear``
     holding the packed tensors (bias kept, in the linear's dtype); every other
     tensor is loaded as is.  A linear with ``<name>.lr_a`` / ``<name>.lr_b`` gets
-    them as its low-rank correction.  ``quantize_config.json`` must be a static-group
+    them as its low-rank correction, and one listed in the ``"rotation"`` entry its
+    ``had_sign`` and block (the module then rotates its input).
+    ``quantize_config.json`` must be a static-group
     ``desc_act=false`` configuration with supported bits, and every ``g_idx``
     must be the trivial ``arange(in) // group`` map (act-order checkpoints are
     out of scope).  `device`: where the model is moved (default: it stays).
@@ -168,8 +213,9 @@ def load_quantized(model: torch.nn.Module, path: str, device=None,
                              f"{fmt!r}")
     tensors, qc = read_quantized(path)
     bits, group = int(qc["bits"]), int(qc["group_size"])
+    blocks = _rotation_blocks(qc, tensors)
     if qc.get("checkpoint_format") == "mxfp4":
-        return _load_mx(model, tensors, qc, device, act_format)
+        return _load_mx(model, tensors, qc, device, act_format, blocks)
     if bits not in (2, 3, 4, 8):
         raise ValueError(f"quantize_config.json: bits={bits} is not one of 2, 3, 4, 8")
     if qc.get("desc_act", False):
@@ -200,11 +246,12 @@ def load_quantized(model: torch.nn.Module, path: str, device=None,
         if bias is not None:
             bias = bias.to(lin.bias.dtype)
         lowrank = _lowrank_of(tensors, name, keys)
+        rotation = _rotation_of(tensors, name, blocks, keys)
         try:
             q = QuantLinear.from_packed(tensors[keys["qweight"]], tensors[keys["qzeros"]],
                                         tensors[keys["scales"]], bits, group, bias=bias,
                                         g_idx=tensors[keys["g_idx"]], device=lin.weight.device,
-                                        lowrank=lowrank)
+                                        lowrank=lowrank, rotation=rotation)
         except ValueError as e:
             raise ValueError(f"{name}: {e}") from None
         if (q.out_features, q.in_features) != (lin.out_features, lin.in_features):
@@ -216,7 +263,7 @@ def load_quantized(model: torch.nn.Module, path: str, device=None,
 
 
 def _load_mx(model: torch.nn.Module, tensors: Dict[str, torch.Tensor], qc: Dict[str, Any],
-             device, act_format=None) -> torch.nn.Module:
+             device, act_format=None, blocks=None) -> torch.nn.Module:
     """load_quantized for ``checkpoint_format: "mxfp4"``: every ``nn.Linear``
     with a ``<name>.qweight`` becomes a ``qlinear.MXQuantLinear``."""
     from .qlinear import MXQuantLinear
@@ -243,10 +290,12 @@ def _load_mx(model: torch.nn.Module, tensors: Dict[str, torch.Tensor], qc: Dict[
         if bias is not None:
             bias = bias.to(lin.bias.dtype)
         lowrank = _lowrank_of(tensors, name, keys)
+        rotation = _rotation_of(tensors, name, blocks or {}, keys)
         try:
             q = MXQuantLinear.from_packed(tensors[keys["qweight"]], tensors[keys["scales"]],
                                           bias=bias, device=lin.weight.device,
-                                          act_format=act_format, lowrank=lowrank)
+                                          act_format=act_format, lowrank=lowrank,
+                                          rotation=rotation)
         except ValueError as e:
             raise ValueError(f"{name}: {e}") from None
         if (q.out_features, q.in_features) != (lin.out_features, lin.in_features):

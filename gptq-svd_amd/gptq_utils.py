@@ -28,7 +28,7 @@ __all__ = [
     "HessianAccumulator", "process_hessian_alt", "process_hessian", "Quantizer", "gptq_fwrd",
     "triton_process_block", "log_quantization_error", "next_power_of_2",
     "truncated_spectral_factor", "pack_quantized", "Sketcher", "process_sketch",
-    "lowrank_correction",
+    "lowrank_correction", "HadamardRotation",
 ]
 
 
@@ -745,3 +745,76 @@ def lowrank_correction(E: torch.Tensor, r: int, *, H: Optional[torch.Tensor] = N
     mu, err0 = host[:r].copy(), float(host[r])
     info = dict(mu=mu, err0=err0, err1=err0 - float(mu.sum()), rank=int(host[r + 1]))
     return A, B, info
+
+
+# ---------------------------------------------------------------------------
+# A18  randomised Hadamard rotation (new; DESIGN.md "Hadamard rotation")
+# ---------------------------------------------------------------------------
+class HadamardRotation:
+    """Q = diag(s) (I (x) H_block) / sqrt(block) on `n` input features
+    (include/truncgptq.h, A18).  ``x W^T = (x Q)(W Q)^T`` holds exactly and the
+    solver's objective is invariant, so a layer is rotated at the two ends of the
+    solve: ``rows(W)`` and ``hessian_(H)`` (or ``rows`` on the scaled sketch) go
+    in, ``rows(Wq, inverse=True)`` comes back.
+
+    The signs are `sign_bits` (int32, n/32 words, bit j of word i = column
+    32 i + j is negated) or are drawn from ``torch.Generator().manual_seed(seed)``
+    on the CPU as ``randint(0, 2, (n,))``, so a seed fixes them on every machine;
+    exactly one of the two is given.  `block` and `sign_bits` live on `device`."""
+
+    MIN_BLOCK, MAX_BLOCK = 32, 4096
+
+    def __init__(self, n: int, block: int, seed: Optional[int] = None,
+                 sign_bits: Optional[torch.Tensor] = None, device="cuda"):
+        n, block = int(n), int(block)
+        if block < self.MIN_BLOCK or block > self.MAX_BLOCK or block & (block - 1):
+            raise ValueError(f"HadamardRotation: block must be a power of two in "
+                             f"[{self.MIN_BLOCK}, {self.MAX_BLOCK}], got {block}")
+        if n <= 0 or n % block:
+            raise ValueError(f"HadamardRotation: block {block} does not divide n = {n}")
+        if (seed is None) == (sign_bits is None):
+            raise ValueError("HadamardRotation: give exactly one of seed and sign_bits")
+        if sign_bits is None:
+            neg = torch.randint(0, 2, (n,), generator=torch.Generator().manual_seed(int(seed)))
+            words = (neg.reshape(-1, 32) << torch.arange(32, dtype=torch.int64)).sum(dim=1)
+            sign_bits = (words - ((words >> 31) << 32)).to(torch.int32)   # two's complement
+        elif sign_bits.dtype != torch.int32 or tuple(sign_bits.shape) != (n // 32,):
+            raise ValueError(f"HadamardRotation: sign_bits must be int32 of {n // 32} words, got "
+                             f"{sign_bits.dtype} {tuple(sign_bits.shape)}")
+        self.n, self.block = n, block
+        self.sign_bits = sign_bits.detach().to(device).contiguous()
+
+    @classmethod
+    def auto_block(cls, n: int) -> int:
+        """The largest power of two that divides n, capped at 4096."""
+        n = int(n)
+        b = min(n & -n, cls.MAX_BLOCK) if n > 0 else 0
+        if b < cls.MIN_BLOCK:
+            raise ValueError(f"HadamardRotation: n = {n} has no power-of-two factor of at least "
+                             f"{cls.MIN_BLOCK}")
+        return b
+
+    def rows(self, X: torch.Tensor, inverse: bool = False,
+             out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+        """``X Q`` (``X Q^T`` with `inverse`) on the last dim, a new tensor of
+        `out_dtype` (default: X's)."""
+        from .qlinear import hadamard
+        _lib.require_cuda(X, "HadamardRotation.rows input")
+        _lib.require_cuda(self.sign_bits, "HadamardRotation.sign_bits")
+        if X.shape[-1] != self.n:
+            raise ValueError(f"HadamardRotation.rows: last dim {X.shape[-1]} != n = {self.n}")
+        return hadamard(X, self.block, self.sign_bits, inverse=inverse, dtype=out_dtype)
+
+    def hessian_(self, H: torch.Tensor) -> torch.Tensor:
+        """``H <- Q^T H Q`` in place (float64, n x n, unit column stride); exactly
+        symmetric.  Returns H."""
+        _lib.require_cuda(H, "HadamardRotation.hessian_ input")
+        _lib.require_cuda(self.sign_bits, "HadamardRotation.sign_bits")
+        if H.dim() != 2 or tuple(H.shape) != (self.n, self.n) or H.dtype != torch.float64 \
+                or H.stride(1) != 1:
+            raise ValueError(f"HadamardRotation.hessian_: H must be float64 ({self.n}, {self.n}) "
+                             f"with unit column stride")
+        with torch.cuda.device(H.device):
+            call("tg_hadamard_sym", stream(), ptr(H), self.n, H.stride(0), self.block,
+                 ptr(self.sign_bits))
+        return H

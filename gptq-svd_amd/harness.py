@@ -56,8 +56,8 @@ import torch
 from torch import nn
 
 from . import dist as tgdist
-from .gptq_utils import (LOWRANK_MAX, HessianAccumulator, Quantizer, Sketcher, gptq_fwrd,
-                         log_quantization_error, lowrank_correction, pack_quantized,
+from .gptq_utils import (LOWRANK_MAX, HadamardRotation, HessianAccumulator, Quantizer, Sketcher,
+                         gptq_fwrd, log_quantization_error, lowrank_correction, pack_quantized,
                          process_hessian, process_hessian_alt, process_sketch)
 
 __all__ = ["get_layers", "get_sequenced_groups", "capture_initial_inputs", "quantize_model",
@@ -323,6 +323,29 @@ def quantize_linear_sharded(W: torch.Tensor, R: torch.Tensor, perm: torch.Tensor
     return Wq, k, q
 
 
+def _rotation_seed(rotate_seed: int, layer: int, group: int) -> int:
+    """The seed of the rotation of sequenced group `group` of decoder layer `layer`."""
+    return (int(rotate_seed) * 65536 + int(layer)) * 16 + int(group)
+
+
+def _check_rotate(model: nn.Module, rotate: int) -> None:
+    """ValueError unless every quantised linear's in_features takes the block
+    (`rotate` > 0: that block; < 0: its automatic block)."""
+    if rotate > 0 and (rotate < HadamardRotation.MIN_BLOCK or rotate > HadamardRotation.MAX_BLOCK
+                       or rotate & (rotate - 1)):
+        raise ValueError(f"rotate must be 0, -1 or a power of two in [{HadamardRotation.MIN_BLOCK}"
+                         f", {HadamardRotation.MAX_BLOCK}], got {rotate}")
+    for i, layer in enumerate(get_layers(model)):
+        for names in get_sequenced_groups(layer):
+            for name in names:
+                n_in = _submodule(layer, name).weight.shape[1]
+                if rotate < 0:
+                    HadamardRotation.auto_block(n_in)       # raises below 32
+                elif n_in % rotate:
+                    raise ValueError(f"rotate={rotate} does not divide in_features={n_in} of "
+                                     f"layer_{i}.{name}")
+
+
 @torch.no_grad()
 def quantize_model(model: nn.Module, input_ids_list: Sequence[torch.Tensor], mode: str = "eigh",
                    w_bits: int = 4, group_size: int = -1, sym: bool = False, eps: float = 1e-2,
@@ -336,7 +359,8 @@ def quantize_model(model: nn.Module, input_ids_list: Sequence[torch.Tensor], mod
                    sketch_seed: Optional[int] = None, clip_search: bool = False,
                    clip_grid: int = 100, clip_steps: int = 80,
                    weight_format: str = "int", lowrank: int = 0,
-                   lowrank_dtype: torch.dtype = torch.float16) -> Dict[str, Any]:
+                   lowrank_dtype: torch.dtype = torch.float16, rotate: int = 0,
+                   rotate_seed: int = 0) -> Dict[str, Any]:
     """Quantise every sequenced linear of `model` in place (layer by layer).
 
     mode "eigh" = TruncGPTQ (process_hessian_alt + gptq_fwrd(use_triton=True));
@@ -381,6 +405,27 @@ def quantize_model(model: nn.Module, input_ids_list: Sequence[torch.Tensor], mod
     r is capped at min(out, in) per module.  Works with `weight_format` and
     `clip_search`; 0 (default) leaves the run bit for bit as it was; single
     process only (ValueError before any work in the multi-GPU mode).
+    `rotate` (A18): a randomised block-Hadamard rotation Q of every quantised
+    linear's input side (``HadamardRotation``), which spreads outlier columns of
+    W and hot activations over their block before the grid sees them.  0 (default)
+    is off and leaves the run bit for bit as it was; -1 takes per group the
+    largest power of two that divides in_features, capped at 4096; any other
+    value is a fixed block, which must be a power of two in [32, 4096] dividing
+    every quantised linear's in_features (ValueError before any work).  Each
+    sequenced group builds one rotation, its seed derived from `rotate_seed`, the
+    layer index and the group index (``_rotation_seed``), and rotates what
+    describes H straight after it is formed: ``hessian_(H)`` in modes "eigh" and
+    "gptq", ``rows`` on the scaled sketch in mode "svd" (Y Q is the sketch of the
+    rotated inputs); the clip search's column weights and the low-rank
+    correction's H are then the rotated quantities.  Each module quantises
+    W' = rows(W) in fp32; the packed tensors and ``lr_a`` / ``lr_b`` are those of
+    W'.  The dense weight written back is in the original basis,
+    rows(Wq', inverse=True), plus A (B Q^T) with `lowrank`, so later layers
+    calibrate on, to fp16 rounding, what the packed model computes.  With
+    ``pack=True`` the module's entry gains ``had_sign`` and ``had_block``; every
+    ``layer_stats`` entry gains ``rotate_block``.  Works in all three modes, with
+    both weight formats, `clip_search` and `lowrank`; single process only
+    (ValueError before any work in the multi-GPU mode).
     `offload`: move each layer to `device` for its turn and back to the CPU
     afterwards (the reference's policy, quantize.py:101, :239); by default
     the model stays where it is (a whole 8B/70B model fits in 288 GB).
@@ -427,6 +472,13 @@ def quantize_model(model: nn.Module, input_ids_list: Sequence[torch.Tensor], mod
                              f"{lowrank_dtype}")
         if _world(pg)[0] > 1:
             raise ValueError("lowrank is single-process")
+    rotate = int(rotate)
+    if rotate:
+        if _world(pg)[0] > 1:
+            raise ValueError("rotate is single-process")
+        _check_rotate(model, rotate)
+    # passed on only when the rotation is on, so a run without it is unchanged
+    rot_kw = dict(rotate=rotate, rotate_seed=int(rotate_seed)) if rotate else {}
     # passed on only when the correction is on, so a run without it is unchanged
     lr_kw = dict(lowrank=lowrank, lowrank_dtype=lowrank_dtype) if lowrank else {}
     # passed on only for MX, so an integer run is unchanged
@@ -445,7 +497,7 @@ def quantize_model(model: nn.Module, input_ids_list: Sequence[torch.Tensor], mod
                              batch_size=batch_size, device=device, block_size=block_size,
                              pack=pack, offload=offload, pg=pg, early_stop=early_stop, clock=clock,
                              staged=staged, sketch_ratio=sketch_ratio, sketch_seed=sketch_seed,
-                             **clip_kw, **fmt_kw, **lr_kw)
+                             **clip_kw, **fmt_kw, **lr_kw, **rot_kw)
         return res
     t_start = time.time()
     world, rank = _world(pg)
@@ -505,7 +557,7 @@ def quantize_model(model: nn.Module, input_ids_list: Sequence[torch.Tensor], mod
                             seed=sketch_seed)
         return HessianAccumulator(in_features, device=device)
 
-    def solve_group(i, layer, names, acc):
+    def solve_group(i, layer, names, acc, gi):
         """All-reduce, factorise and quantise one sequenced group."""
         cur_eps = adaptive_eps(names[0], eps) if use_adaptive_eps else eps
         ev = clock.start() if clock else None
@@ -515,6 +567,14 @@ def quantize_model(model: nn.Module, input_ids_list: Sequence[torch.Tensor], mod
             clock.stop("allreduce", ev)
             ev = clock.start()
         H = acc.get_scaled_sketch() if mode == "svd" else acc.get_hessian()
+        rot = None
+        if rotate:
+            n_in = H.shape[1]
+            rot = HadamardRotation(n_in, HadamardRotation.auto_block(n_in) if rotate < 0
+                                   else rotate, seed=_rotation_seed(rotate_seed, i, gi),
+                                   device=H.device)
+            # Y Q is the sketch of the rotated inputs; Q^T H Q their Hessian
+            H = rot.rows(H) if mode == "svd" else rot.hessian_(H)
         if mode == "svd":
             logging.info(f"   Processing Sketch (Shape: {tuple(H.shape)})")
             R, perm = process_sketch(H, threshold=cur_eps, threshold_method=threshold_method)
@@ -557,16 +617,28 @@ def quantize_model(model: nn.Module, input_ids_list: Sequence[torch.Tensor], mod
                 if R_x is not None and rank == 0:
                     log_quantization_error(W, Wq, R_x, perm)
             else:
-                Wq, k = gptq_fwrd(sub.weight.data.float(), R, q, perm,
+                W = sub.weight.data.float()
+                if rot is not None:
+                    W = rot.rows(W)
+                Wq, k = gptq_fwrd(W, R, q, perm,
                                   block_size=block_size, use_triton=(mode != "gptq"), R_x=R_x)
+                del W
             if lr_h is not None:
                 from .qlinear import add_lowrank
                 W = sub.weight.data.float()
+                if rot is not None:
+                    W = rot.rows(W)
                 lr_a, lr_b, lr_info = lowrank_correction(W - Wq.float(), min(lowrank, *W.shape),
                                                          **lr_h)
                 lr_a, lr_b = lr_a.to(lowrank_dtype), lr_b.to(lowrank_dtype)
-                Wq = add_lowrank(Wq.float(), lr_a, lr_b)
+                if rot is None:
+                    Wq = add_lowrank(Wq.float(), lr_a, lr_b)
                 del W
+            if rot is not None:
+                # back to the original basis: Wq' Q^T (+ A (B Q^T))
+                Wq = rot.rows(Wq.float(), inverse=True)
+                if lr_h is not None:
+                    Wq = add_lowrank(Wq, lr_a, rot.rows(lr_b.float(), inverse=True))
             sub.weight.copy_(Wq)
             full = f"layer_{i}.{name}"
             if pack:
@@ -574,12 +646,17 @@ def quantize_model(model: nn.Module, input_ids_list: Sequence[torch.Tensor], mod
                 packed[qual.get(id(sub), full)] = dict(qweight=qw, qzeros=qz, scales=sc)
                 if lr_h is not None:
                     packed[qual.get(id(sub), full)].update(lr_a=lr_a, lr_b=lr_b)
+                if rot is not None:
+                    packed[qual.get(id(sub), full)].update(had_sign=rot.sign_bits,
+                                                           had_block=rot.block)
             dt = time.time() - t0
             used = k if mode != "gptq" else "N/A"
             logging.info(f"   {name: <15} | Rank: {str(used): <4} | Time: {dt:.2f}s")
             entry = {"name": full, "rank": used, "time": dt}
             if fmt_kw:
                 entry["weight_format"] = weight_format
+            if rot is not None:
+                entry["rotate_block"] = rot.block
             if clip_search:
                 j0, j1 = q.clip_objective.sum(dim=(0, 1)).tolist()
                 moved = int((q.clip_choice != 0).sum().item())
@@ -622,7 +699,7 @@ def quantize_model(model: nn.Module, input_ids_list: Sequence[torch.Tensor], mod
                 hook.remove()
             if clock:
                 clock.stop("calib_forward", ev)
-            solve_group(i, layer, names, acc)
+            solve_group(i, layer, names, acc, gi)
             del acc
         ev = clock.start() if clock else None
         run_layer(layer, outs)
@@ -678,7 +755,7 @@ def quantize_model(model: nn.Module, input_ids_list: Sequence[torch.Tensor], mod
                     add(acc, d)
             if clock:
                 clock.stop("calib_forward", ev)
-            solve_group(i, layer, names, acc)
+            solve_group(i, layer, names, acc, gi)
             del acc
         ev = clock.start() if clock else None
         for bi, (j, x, kwb) in enumerate(batches()):
@@ -748,6 +825,8 @@ def run_and_record(model: nn.Module, input_ids_list: Sequence[torch.Tensor], sav
     if kw.get("lowrank"):
         cfg.update(lowrank=int(kw["lowrank"]),
                    lowrank_dtype=str(kw.get("lowrank_dtype", torch.float16)).replace("torch.", ""))
+    if kw.get("rotate"):
+        cfg.update(rotate=int(kw["rotate"]), rotate_seed=int(kw.get("rotate_seed", 0)))
     mid = getattr(getattr(model, "config", None), "_name_or_path", None)
     if mid:
         cfg["model_id"] = mid
@@ -792,6 +871,8 @@ def _packed_copy(model: nn.Module, res: Dict[str, Any], save_path: str,
         extra.update(_clip_settings(kw))
     if kw.get("lowrank"):
         extra["lowrank_dtype"] = str(kw.get("lowrank_dtype", torch.float16)).replace("torch.", "")
+    if kw.get("rotate"):
+        extra.update(rotate=int(kw["rotate"]), rotate_seed=int(kw.get("rotate_seed", 0)))
     if kw.get("weight_format", "int") == "mxfp4":
         save_quantized(path, model, res["packed"], 4, 32, True, extra_config=extra,
                        weight_format="mxfp4")

@@ -29,6 +29,13 @@ Low-rank correction (A17, opt-in): a layer quantised with ``lowrank=r`` carries
 ``y = x W^^T + (x lr_b^T) lr_a^T + bias`` in three calls: the packed GEMM with
 fp32 output and no bias, ``tg_lr_down`` and ``tg_lr_finish``.  Without the two
 buffers the forward is the single call it was.
+
+Hadamard rotation (A18, opt-in): a layer quantised with ``rotate`` stores the
+weight of the rotated basis, W' = W Q, and carries ``had_sign`` (int32, in/32
+words of sign bits) and ``rotate_block``.  Its forward first computes
+``x' = x Q`` in the activation dtype (``hadamard``, one ``tg_hadamard`` launch)
+and feeds x' to everything that took x: ``y = x' W'^^T (+ (x' lr_b^T) lr_a^T)
++ bias``.
 """
 from __future__ import annotations
 
@@ -41,7 +48,7 @@ from ._lib import (ACT_FORMATS, DTYPES, TG_FMT_MXFP4, call, lib, ptr, require_cu
                    workspace)
 
 __all__ = ["QuantLinear", "dequantize_packed", "MXQuantLinear", "dequantize_packed_mx",
-           "quantize_act_mx", "dequantize_act_mx", "add_lowrank"]
+           "quantize_act_mx", "dequantize_act_mx", "add_lowrank", "hadamard"]
 
 _BITS = (2, 3, 4, 8)
 
@@ -87,6 +94,87 @@ def dequantize_packed(qweight: torch.Tensor, qzeros: torch.Tensor, scales: torch
         call("tg_dequant_packed", stream(), ptr(qweight), ptr(qzeros), ptr(scales),
              DTYPES[scales.dtype], m, n, g, w_bits, ptr(out), DTYPES[dtype], n)
     return out
+
+
+# ---------------------------------------------------------------------------
+# Hadamard rotation (A18)
+# ---------------------------------------------------------------------------
+_HAD_DTYPES = (torch.float16, torch.bfloat16, torch.float32, torch.float64)
+
+
+def _check_block(block: int, n: int) -> int:
+    block = int(block)
+    if block < 32 or block > 4096 or block & (block - 1):
+        raise ValueError(f"Hadamard block must be a power of two in [32, 4096], got {block}")
+    if n % block:
+        raise ValueError(f"Hadamard block {block} does not divide the width {n}")
+    return block
+
+
+def hadamard(x: torch.Tensor, block: int, sign_bits: Optional[torch.Tensor],
+             inverse: bool = False, dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """``x Q`` (``x Q^T`` with `inverse`) on the last dim, Q the randomised block
+    Hadamard matrix of `block` and `sign_bits` (int32, n/32 words, bit j of word i
+    = column 32 i + j is negated; None = all +): one ``tg_hadamard`` launch.
+    fp16 / bf16 / fp32 inputs compute in fp32 and round once to `dtype` (default:
+    the input's; one of those three); float64 stays float64."""
+    require_cuda(x, "hadamard input")
+    if x.dtype not in _HAD_DTYPES:
+        raise RuntimeError(f"hadamard takes float16, bfloat16, float32 or float64, got {x.dtype}")
+    dtype = x.dtype if dtype is None else dtype
+    if dtype not in _HAD_DTYPES or (dtype == torch.float64) != (x.dtype == torch.float64):
+        raise ValueError(f"hadamard: output dtype {dtype} does not go with input dtype {x.dtype}")
+    n = x.shape[-1]
+    block = _check_block(block, n)
+    if sign_bits is not None:
+        require_cuda(sign_bits, "hadamard sign_bits")
+        if sign_bits.dtype != torch.int32 or tuple(sign_bits.shape) != (n // 32,):
+            raise ValueError(f"sign_bits must be int32 of {n // 32} words, got {sign_bits.dtype} "
+                             f"{tuple(sign_bits.shape)}")
+        sign_bits = sign_bits.contiguous()
+    x2 = x.reshape(-1, n)
+    T = x2.shape[0]
+    y = torch.empty((T, n), dtype=dtype, device=x.device)
+    if T > 0:
+        if x2.stride(1) != 1 or (T > 1 and x2.stride(0) < n):
+            x2 = x2.contiguous()
+        ldx = x2.stride(0) if T > 1 else n
+        with torch.cuda.device(x.device):
+            call("tg_hadamard", stream(), ptr(x2), DTYPES[x.dtype], T, n, ldx, block,
+                 ptr(sign_bits), int(bool(inverse)), ptr(y), DTYPES[dtype], n)
+    return y.reshape(x.shape)
+
+
+def _rotate_rows(x2: torch.Tensor, T: int, n: int, ldx: int, block: int,
+                 sign_bits: torch.Tensor) -> torch.Tensor:
+    """x2 Q in x2's dtype, (T, n) contiguous: the one launch a rotated forward adds."""
+    xr = torch.empty((T, n), dtype=x2.dtype, device=x2.device)
+    with torch.cuda.device(x2.device):
+        call("tg_hadamard", stream(), ptr(x2), DTYPES[x2.dtype], T, n, ldx, block, ptr(sign_bits),
+             0, ptr(xr), DTYPES[x2.dtype], n)
+    return xr
+
+
+def _register_rotation(mod: nn.Module, block: int, device) -> None:
+    """``rotate_block`` and the buffer ``had_sign`` (int32, in/32 words) for
+    block > 0; the attribute is None otherwise, like an absent bias."""
+    mod.rotate_block = int(block)
+    if mod.rotate_block:
+        _check_block(block, mod.in_features)
+        mod.register_buffer("had_sign", torch.zeros(mod.in_features // 32, dtype=torch.int32,
+                                                    device=device))
+    else:
+        mod.had_sign = None
+
+
+def _check_rotation(rotation, n: int):
+    """(block, sign_bits) of a ``rotation=`` argument, checked against the width."""
+    block, sign = rotation
+    block = _check_block(block, n)
+    if sign.dtype != torch.int32 or tuple(sign.shape) != (n // 32,):
+        raise ValueError(f"rotation sign_bits must be int32 of {n // 32} words, got {sign.dtype} "
+                         f"{tuple(sign.shape)}")
+    return block, sign
 
 
 # ---------------------------------------------------------------------------
@@ -176,7 +264,7 @@ class QuantLinear(nn.Module):
     def __init__(self, in_features: int, out_features: int, w_bits: int, group_size: int,
                  bias: bool = False, scale_dtype: torch.dtype = torch.float16,
                  bias_dtype: torch.dtype = torch.float16, device=None, lowrank: int = 0,
-                 lowrank_dtype: torch.dtype = torch.float16):
+                 lowrank_dtype: torch.dtype = torch.float16, rotate_block: int = 0):
         super().__init__()
         if w_bits not in _BITS:
             raise ValueError(f"w_bits must be one of {_BITS}, got {w_bits}")
@@ -202,18 +290,23 @@ class QuantLinear(nn.Module):
         else:
             self.bias = None
         _register_lowrank(self, int(lowrank), lowrank_dtype, device)
+        _register_rotation(self, rotate_block, device)
 
     @classmethod
     def from_packed(cls, qweight: torch.Tensor, qzeros: torch.Tensor, scales: torch.Tensor,
                     w_bits: int, group_size: int, bias: Optional[torch.Tensor] = None,
                     g_idx: Optional[torch.Tensor] = None, device=None,
-                    lowrank=None) -> "QuantLinear":
+                    lowrank=None, rotation=None) -> "QuantLinear":
         """From the packed tensors (a checkpoint's, or ``pack_quantized``'s).
         `g_idx`, when given, must be the trivial ``arange(in) // group``.
-        ``lowrank=(A, B)``: the correction's factors, (out, r) and (r, in)."""
+        ``lowrank=(A, B)``: the correction's factors, (out, r) and (r, in).
+        ``rotation=(block, sign_bits)``: the packed weight is that of the rotated
+        basis and the forward rotates x first."""
         m, n, g = _shapes(qweight, qzeros, scales, w_bits, group_size)
         if lowrank is not None:
             lowrank = _check_lowrank(lowrank, m, n)
+        if rotation is not None:
+            rotation = _check_rotation(rotation, n)
         if g_idx is not None:
             triv = torch.arange(n, dtype=torch.int64) // g
             if tuple(g_idx.shape) != (n,) or not torch.equal(g_idx.cpu().to(torch.int64), triv):
@@ -223,7 +316,8 @@ class QuantLinear(nn.Module):
         q = cls(n, m, w_bits, group_size, bias=bias is not None, scale_dtype=scales.dtype,
                 bias_dtype=bias.dtype if bias is not None else torch.float16, device=dev,
                 lowrank=lowrank[0].shape[1] if lowrank is not None else 0,
-                lowrank_dtype=lowrank[0].dtype if lowrank is not None else torch.float16)
+                lowrank_dtype=lowrank[0].dtype if lowrank is not None else torch.float16,
+                rotate_block=rotation[0] if rotation is not None else 0)
         q.qweight.copy_(qweight)
         q.qzeros.copy_(qzeros)
         q.scales.copy_(scales)
@@ -232,24 +326,37 @@ class QuantLinear(nn.Module):
         if lowrank is not None:
             q.lr_a.copy_(lowrank[0].detach())
             q.lr_b.copy_(lowrank[1].detach())
+        if rotation is not None:
+            q.had_sign.copy_(rotation[1])
         return q
 
     def extra_repr(self) -> str:
         lr = f", lowrank={self.lr_a.shape[1]}" if self.lr_a is not None else ""
+        if self.rotate_block:
+            lr += f", rotate_block={self.rotate_block}"
         return (f"in_features={self.in_features}, out_features={self.out_features}, "
                 f"bits={self.w_bits}, group_size={self.group_size}, "
                 f"bias={self.bias is not None}{lr}")
 
-    def dequantize(self, dtype: torch.dtype = torch.float16,
-                   effective: bool = False) -> torch.Tensor:
+    def dequantize(self, dtype: torch.dtype = torch.float16, effective: bool = False,
+                   rotated: bool = True) -> torch.Tensor:
         """The dense (out, in) weight; ``effective=True`` adds the low-rank
-        correction, W^ + lr_a lr_b (``add_lowrank``), when the layer has one."""
+        correction, W^ + lr_a lr_b (``add_lowrank``), when the layer has one.
+        A rotated layer stores the weight of the rotated basis, and that is what
+        ``rotated=True`` returns; ``rotated=False`` returns R^-1 of it (computed
+        from the fp32 matrix, rounded once to `dtype`), the matrix for which
+        ``x @ W.T`` approximates the forward."""
+        back = self.rotate_block and not rotated
+        dt = torch.float32 if back else dtype
         if effective and self.lr_a is not None:
             W = dequantize_packed(self.qweight, self.qzeros, self.scales, self.w_bits,
                                   self.group_size, torch.float32)
-            return add_lowrank(W, self.lr_a, self.lr_b, dtype)
-        return dequantize_packed(self.qweight, self.qzeros, self.scales, self.w_bits,
-                                 self.group_size, dtype)
+            W = add_lowrank(W, self.lr_a, self.lr_b, dt)
+        else:
+            W = dequantize_packed(self.qweight, self.qzeros, self.scales, self.w_bits,
+                                  self.group_size, dt)
+        return hadamard(W, self.rotate_block, self.had_sign, inverse=True, dtype=dtype) \
+            if back else W
 
     @torch.no_grad()
     def forward(self, x: torch.Tensor) -> torch.Tensor:
@@ -269,6 +376,8 @@ class QuantLinear(nn.Module):
             if x2.stride(1) != 1 or (T > 1 and x2.stride(0) < n):
                 x2 = x2.contiguous()
             ldx = x2.stride(0) if T > 1 else n
+            if self.rotate_block:
+                x2, ldx = _rotate_rows(x2, T, n, ldx, self.rotate_block, self.had_sign), n
             bias = self.bias
             lr = self.lr_a is not None
             # with a correction the GEMM leaves its fp32 sums; tg_lr_finish adds the bias
@@ -383,7 +492,8 @@ class MXQuantLinear(nn.Module):
 
     def __init__(self, in_features: int, out_features: int, bias: bool = False,
                  bias_dtype: torch.dtype = torch.float16, device=None, act_format=None,
-                 lowrank: int = 0, lowrank_dtype: torch.dtype = torch.float16):
+                 lowrank: int = 0, lowrank_dtype: torch.dtype = torch.float16,
+                 rotate_block: int = 0):
         super().__init__()
         _check_act_format(act_format)
         self.act_format = act_format
@@ -401,22 +511,28 @@ class MXQuantLinear(nn.Module):
         else:
             self.bias = None
         _register_lowrank(self, int(lowrank), lowrank_dtype, device)
+        _register_rotation(self, rotate_block, device)
 
     @classmethod
     def from_packed(cls, qweight: torch.Tensor, scales: torch.Tensor,
                     bias: Optional[torch.Tensor] = None, device=None,
-                    act_format=None, lowrank=None) -> "MXQuantLinear":
+                    act_format=None, lowrank=None, rotation=None) -> "MXQuantLinear":
         """From the packed pair (a checkpoint's, or ``pack_quantized``'s).
-        ``lowrank=(A, B)``: the correction's factors, (out, r) and (r, in)."""
+        ``lowrank=(A, B)``: the correction's factors, (out, r) and (r, in).
+        ``rotation=(block, sign_bits)``: the packed weight is that of the rotated
+        basis and the forward rotates x first."""
         m, n = _shapes_mx(qweight, scales)
         if lowrank is not None:
             lowrank = _check_lowrank(lowrank, m, n)
+        if rotation is not None:
+            rotation = _check_rotation(rotation, n)
         dev = device if device is not None else qweight.device
         q = cls(n, m, bias=bias is not None,
                 bias_dtype=bias.dtype if bias is not None else torch.float16, device=dev,
                 act_format=act_format,
                 lowrank=lowrank[0].shape[1] if lowrank is not None else 0,
-                lowrank_dtype=lowrank[0].dtype if lowrank is not None else torch.float16)
+                lowrank_dtype=lowrank[0].dtype if lowrank is not None else torch.float16,
+                rotate_block=rotation[0] if rotation is not None else 0)
         q.qweight.copy_(qweight)
         q.scales.copy_(scales)
         if bias is not None:
@@ -424,21 +540,34 @@ class MXQuantLinear(nn.Module):
         if lowrank is not None:
             q.lr_a.copy_(lowrank[0].detach())
             q.lr_b.copy_(lowrank[1].detach())
+        if rotation is not None:
+            q.had_sign.copy_(rotation[1])
         return q
 
     def extra_repr(self) -> str:
         lr = f", lowrank={self.lr_a.shape[1]}" if self.lr_a is not None else ""
+        if self.rotate_block:
+            lr += f", rotate_block={self.rotate_block}"
         return (f"in_features={self.in_features}, out_features={self.out_features}, "
                 f"format=mxfp4, bias={self.bias is not None}, act_format={self.act_format}{lr}")
 
-    def dequantize(self, dtype: torch.dtype = torch.float16,
-                   effective: bool = False) -> torch.Tensor:
+    def dequantize(self, dtype: torch.dtype = torch.float16, effective: bool = False,
+                   rotated: bool = True) -> torch.Tensor:
         """The dense (out, in) weight; ``effective=True`` adds the low-rank
-        correction, W^ + lr_a lr_b (``add_lowrank``), when the layer has one."""
+        correction, W^ + lr_a lr_b (``add_lowrank``), when the layer has one.
+        A rotated layer stores the weight of the rotated basis, and that is what
+        ``rotated=True`` returns; ``rotated=False`` returns R^-1 of it (computed
+        from the fp32 matrix, rounded once to `dtype`), the matrix for which
+        ``x @ W.T`` approximates the forward."""
+        back = self.rotate_block and not rotated
+        dt = torch.float32 if back else dtype
         if effective and self.lr_a is not None:
-            return add_lowrank(dequantize_packed_mx(self.qweight, self.scales, torch.float32),
-                               self.lr_a, self.lr_b, dtype)
-        return dequantize_packed_mx(self.qweight, self.scales, dtype)
+            W = add_lowrank(dequantize_packed_mx(self.qweight, self.scales, torch.float32),
+                            self.lr_a, self.lr_b, dt)
+        else:
+            W = dequantize_packed_mx(self.qweight, self.scales, dt)
+        return hadamard(W, self.rotate_block, self.had_sign, inverse=True, dtype=dtype) \
+            if back else W
 
     @torch.no_grad()
     def forward(self, x: torch.Tensor) -> torch.Tensor:
@@ -458,6 +587,8 @@ class MXQuantLinear(nn.Module):
             if x2.stride(1) != 1 or (T > 1 and x2.stride(0) < n):
                 x2 = x2.contiguous()
             ldx = x2.stride(0) if T > 1 else n
+            if self.rotate_block:
+                x2, ldx = _rotate_rows(x2, T, n, ldx, self.rotate_block, self.had_sign), n
             bias = self.bias
             lr = self.lr_a is not None
             # with a correction the GEMM leaves its fp32 sums; tg_lr_finish adds the bias.

@@ -632,6 +632,44 @@ int tg_lr_finish(void *stream, const float *Y32, int64_t stride_y32, const float
                  int64_t stride_z, const void *A, int a_dtype, int64_t stride_a, int T, int m,
                  int r, const void *bias, int bias_dtype, void *Y, int y_dtype, int64_t stride_y);
 
+/* ---- A18: randomised block-Hadamard rotation (new; the reference's roadmap
+ * lists it as "integration with QuIP#") -----------------------------------------
+ * Q = diag(s) (I_{n/b} (x) H_b) c, with b = block a power of two in [32, 4096]
+ * that divides n, H_b the Sylvester Hadamard matrix, c = 1/sqrt(b) and s in
+ * {+1, -1}^n.  x W^T = (x Q)(W Q)^T holds exactly, and the rotated W and H have
+ * no outlier columns (DESIGN.md "Hadamard rotation").
+ * sign_bits: n / 32 int32 words of device memory, bit j of word i set = column
+ * 32 i + j is negated; null = all signs +.
+ * The row operator R(x) = x Q, operation by operation (the host restatement is
+ * bit-equal, tests/had_ref.py):
+ *   1. x is converted exactly to the compute type, f64 for TG_F64 input and f32
+ *      otherwise;
+ *   2. every element is multiplied by its sign (exact);
+ *   3. inside each block of b consecutive columns the stages h = 1, 2, 4, ...
+ *      b/2 run in that order; stage h turns every pair (j, j + h) with
+ *      (j mod 2h) < h into (u + v, u - v), each one correctly rounded operation;
+ *   4. one multiply by c = (float)(1.0 / sqrt((double)b)), or its f64 form (a
+ *      power of two when log2 b is even);
+ *   5. one round-to-nearest-even to the output type.
+ * The inverse R^-1(y) = y Q^T has the same steps 1, 3 and 4 and multiplies by
+ * the signs after the scale.
+ * tg_hadamard applies R (inverse = 0) or R^-1 to each of `rows` rows of X
+ * (x_dtype TG_F16 / TG_BF16 / TG_F32 / TG_F64, row stride stride_x >= n) into Y
+ * (y_dtype TG_F16 / TG_BF16 / TG_F32, or TG_F64 exactly when x_dtype is; row
+ * stride stride_y >= n).  Y may be X when the dtypes and strides are equal.
+ * 16-byte loads and stores are used where the pointer and the row stride in
+ * bytes are multiples of 16, scalar ones otherwise.  One launch, one pass over
+ * memory, bit-identical from call to call.
+ * tg_hadamard_sym: H (n x n f64, row stride stride_h) <- Q^T H Q in place: the
+ * row operator on every row, then the same operator along the row index; the
+ * lower triangle, diagonal included, is what that gives and the upper triangle
+ * is written as its mirror, so H is exactly symmetric.  No workspace. */
+int tg_hadamard(void *stream, const void *X, int x_dtype, int64_t rows, int n, int64_t stride_x,
+                int block, const int32_t *sign_bits, int inverse, void *Y, int y_dtype,
+                int64_t stride_y);
+int tg_hadamard_sym(void *stream, double *H, int n, int64_t stride_h, int block,
+                    const int32_t *sign_bits);
+
 #ifdef __cplusplus
 }
 #endif
