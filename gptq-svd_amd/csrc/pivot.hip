@@ -17,8 +17,10 @@
 //
 // n <= 32768: the candidate-set path.  One workgroup picks a whole panel's
 // pivots among the rows of largest Schur diagonal (piv_sel_kernel: 256, 512
-// or 1024 candidates, the level chosen panel by panel), piv_fill_kernel
-// computes the panel's L columns and diagonals of every row, and a rank-32
+// or 1024 candidates, the level chosen panel by panel), the panel's L columns
+// and diagonals of every row are computed by fill workers in the same launch
+// as the steps go (piv_stream_worker; piv_fill_kernel fills what they left,
+// or everything with TG_PIV_STREAM=0), and a rank-32
 // update on FP64 MFMA writes the next Schur complement, compacted to the
 // unpivoted rows and stored as its lower triangle only, into the other of two
 // n x n buffers (syrk_compact_p_kernel).
@@ -65,6 +67,11 @@ struct PivWs {
   double *Lpp;      // PB x PB  L rows of the panel's pivots (panel columns)
   double *Hk2;      // n x n  second buffer: the compacted Schur complements alternate
   int32_t *oidx;    // n  new position ps + x -> its compact index in the panel's H_k
+  // streamed fill (piv_stream_worker): with prow / pinv / Lpp the ring of step records
+  unsigned long long *strm;  // [0] progress word of the panel in flight (SW_*)
+  int32_t *ppoi;             // PB  compact index of each pivot in the panel's H_k
+  int32_t *pq;               // PB  position each pivot was swapped in from
+  int32_t *fdone;            // ceil(n / 64)  launch number of the panel whose worker filled the chunk
 };
 constexpr int PPS = PB + 8;  // partial / broadcast record (doubles)
 static_assert(PGMAX * PPS % 256 == 0, "slot copy assumes whole rounds of 256 threads");
@@ -108,6 +115,10 @@ void piv_layout(A &ar, int n, int k, PivWs *p) {
   take(q.Lpp, PB * PB);
   take2m(q.Hk2, compact_pivot(n) ? size_t(n) * n : size_t(1));
   take(q.oidx, n);
+  take(q.strm, 2);
+  take(q.ppoi, PB);
+  take(q.pq, PB);
+  take(q.fdone, size_t(tg::cdiv(n, 64)));
 }
 
 // B[t][c] = S[t] * Vh[t][c]    (gptq_utils.py:112)
@@ -622,6 +633,7 @@ __device__ __forceinline__ bool lev_pays(int rem, int lost) {
 struct SelPanel {
   int n, k, ps, pe, nset, bp, brow, bo, lev;
   bool adaptive;
+  bool pub;  // a publisher wave stores the step records (streamed fill), not the stepping waves
   double tau, bv;
   const double *dS;
   const int32_t *pS;
@@ -677,6 +689,29 @@ template <int S>
 __device__ inline int wave_min_stage(int x) {
   return min(x, partner<S>(x));
 }
+// The merge of the NW wave records behind block_argmax_sel's barrier (the
+// publisher wave of a streamed panel runs it too, to follow the steps).
+template <int NW>
+__device__ inline void sel_merge(double &v, int &p, int &r, int &o, const double2 *rec,
+                                 const int *reco) {
+  double2 x[NW];
+#pragma unroll
+  for (int q = 0; q < NW; ++q) x[q] = rec[q];
+  v = x[0].x;
+#pragma unroll
+  for (int q = 1; q < NW; ++q) v = vmax_d(v, x[q].x);
+  p = INT_MAX;
+  r = 0;
+  o = 0;
+#pragma unroll
+  for (int q = 0; q < NW; ++q) {
+    const int op = __double2hiint(x[q].y);
+    const bool take = (x[q].x == v) & (op < p);
+    p = take ? op : p;
+    r = take ? __double2loint(x[q].y) : r;
+    o = take ? reco[q] : o;
+  }
+}
 template <int NW>
 __device__ inline void block_argmax_sel(double &v, int &p, int &r, int &o, double2 *rec,
                                         int *reco) {
@@ -704,23 +739,7 @@ __device__ inline void block_argmax_sel(double &v, int &p, int &r, int &o, doubl
     reco[threadIdx.x >> 6] = wo;
   }
   __syncthreads();
-  double2 x[NW];
-#pragma unroll
-  for (int q = 0; q < NW; ++q) x[q] = rec[q];
-  v = x[0].x;
-#pragma unroll
-  for (int q = 1; q < NW; ++q) v = vmax_d(v, x[q].x);
-  p = INT_MAX;
-  r = 0;
-  o = 0;
-#pragma unroll
-  for (int q = 0; q < NW; ++q) {
-    const int op = __double2hiint(x[q].y);
-    const bool take = (x[q].x == v) & (op < p);
-    p = take ? op : p;
-    r = take ? __double2loint(x[q].y) : r;
-    o = take ? reco[q] : o;
-  }
+  sel_merge<NW>(v, p, r, o, rec, reco);
 }
 
 // Radix-select histograms: 2048 bins padded by one word per 32 (bin b at
@@ -776,11 +795,286 @@ __device__ inline void hist_scan(const unsigned *hist, int target, int *out) {
   }
 }
 
+// The pivot's diagonal entry of L and its reciprocal: one sequence for the
+// stepping waves and the publisher wave, so both hold the same bits.
+__device__ __forceinline__ void piv_scale(double dpiv, double &ljj, double &inv) {
+  ljj = sqrt(fmax(dpiv, 0.0));
+  inv = ljj > 0.0 ? 1.0 / ljj : 0.0;
+}
+
+// ---------------------------------------------------------------------------
+// Streamed fill (TG_PIV_STREAM, default on).  The fill of step t needs only
+// pivot t, so it does not have to wait for the panel's last step: the
+// piv_sel_kernel launch carries fill workers next to the selector, and the
+// selector's publisher wave hands them each step's record as the steps go.
+//
+// Record of step t: prow[t] (pivot row), ppoi[t] (its compact index), pq[t]
+// (the position it was swapped in from), pinv[t], Lpp[t][0..t] -- the arrays
+// piv_fill_kernel reads, so the same bytes serve the net launch below.
+// Progress word strm[0] (one 8-byte sc1 store): launch number | panel start |
+// flags | records complete.  Hand-off in the write-through form
+// (MI355X_MICROARCH.md "Valid forms", row 1): the publisher wave stores a
+// record sc1, drains vmcnt(0) and then stores the word sc1; a worker wave
+// polls the word sc1 and reads every record byte sc1 after its poll matched.
+// The publisher drains one step late (the stores have had a step to land), so
+// it reaches the stepping waves' barriers on time; the stepping waves
+// themselves store nothing to global memory in a streamed panel.
+//
+// A worker is one wave owning the 64 rows at panel-start positions ps + 64 c
+// ..; it runs piv_fill_kernel's sequence for its rows record by record and
+// follows each row through the published swaps (positions i and q).  L goes
+// out four steps at a time; when the panel's end is published the worker
+// writes LT (column = final position - ps2) and dsc, marks its chunk in fdone
+// and counts it in strm[1].  piv_fill_kernel runs after the launch as a net:
+// it returns at once when every chunk is counted, and otherwise fills exactly
+// the rows whose panel-start chunk is not marked (L entries a worker that gave
+// up had written are rewritten with the same values), so the results never
+// depend on co-residency or timing.  One worker per chunk, at most one per
+// CU besides the selector's: chunks beyond that are the net's.  Waits: the selector
+// never waits for a worker; a worker's polls are bounded by `budget` ticks of
+// the 100 MHz clock since its start, after which it leaves without writing
+// (budget 0: at once).  A worker reads perm and dsc of its rows before the
+// selector's tail rewrites perm: the publisher stores the end of the panel
+// and drains before the tail's barrier, and a worker that finds the end
+// already published after loading its rows leaves them to the net.
+typedef __attribute__((address_space(1))) double pv_f64;
+typedef __attribute__((address_space(1))) int32_t pv_i32;
+typedef __attribute__((address_space(1))) unsigned long long pv_u64;
+__device__ __forceinline__ void st_sc1d(double *p, double v) {
+  __hip_atomic_store((pv_f64 *)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ double ld_sc1d(const double *p) {
+  return __hip_atomic_load((pv_f64 *)const_cast<double *>(p), __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void st_sc1i(int32_t *p, int v) {
+  __hip_atomic_store((pv_i32 *)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ int ld_sc1i(const int32_t *p) {
+  return __hip_atomic_load((pv_i32 *)const_cast<int32_t *>(p), __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void st_sc1u(unsigned long long *p, unsigned long long v) {
+  __hip_atomic_store((pv_u64 *)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ unsigned long long ld_sc1u(const unsigned long long *p) {
+  return __hip_atomic_load((pv_u64 *)const_cast<unsigned long long *>(p), __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// progress word: [63:32] launch number (> 0), [31:16] panel start, [7] not
+// streamed, [6] panel ended, [5:0] step records complete (0 .. PB)
+constexpr unsigned long long SW_ENDED = 64ull, SW_NOSTREAM = 128ull, SW_STEPS = 63ull;
+static_assert(PB <= int(SW_STEPS), "step count field");
+__device__ __forceinline__ unsigned long long sw_word(unsigned seq, int ps) {
+  return (static_cast<unsigned long long>(seq) << 32) |
+         (static_cast<unsigned long long>(ps & 0xffff) << 16);
+}
+
+// Publisher wave of a streamed panel (wave 4 of the selector; NW stepping
+// waves).  It joins every barrier of sel_steps<NW, *> -- per step the block
+// argmax's (t > 0) and the hand-off's, then the tail's two -- and between them
+// stores the step's record from what the stepping waves left in LDS (the
+// merged argmax records, the pivot's L row).
+template <int NW>
+__device__ __forceinline__ void sel_publish(const SelPanel &sp, PivWs w, unsigned seq) {
+  const int lane = threadIdx.x & 63;
+  const int ps = sp.ps, pe = sp.pe;
+  const unsigned long long base = sw_word(seq, ps);
+  int piv = sp.brow, q = sp.bp, opiv = sp.bo;
+  double dpiv = sp.bv;
+  int tdone = 0;
+  for (int t = 0; t < PB; ++t) {  // every exit is wave-uniform
+    if (ps + t >= pe) break;
+    if (t > 0) {
+      __syncthreads();  // block_argmax_sel's
+      double v;
+      int p, r, o;
+      sel_merge<NW>(v, p, r, o, sp.rec, sp.reco);
+      v = __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)),
+                           __builtin_amdgcn_readfirstlane(__double2loint(v)));
+      // record t - 1 was stored a step ago: drained by now, publish it
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if (lane == 0) st_sc1u(w.strm, base | static_cast<unsigned long long>(t));
+      if (!(v > sp.tau)) break;
+      dpiv = v;
+      q = __builtin_amdgcn_readfirstlane(p);
+      piv = __builtin_amdgcn_readfirstlane(r);
+      opiv = __builtin_amdgcn_readfirstlane(o);
+    }
+    __syncthreads();  // the step's hand-off: lrow holds the pivot's L row
+    double ljj, inv;
+    piv_scale(dpiv, ljj, inv);
+    if (lane <= t) st_sc1d(w.Lpp + t * PB + lane, lane < t ? sp.lrow[lane] : ljj);
+    if (lane == 0) {
+      st_sc1i(w.prow + t, piv);
+      st_sc1i(w.ppoi + t, opiv);
+      st_sc1i(w.pq + t, q);
+      st_sc1d(w.pinv + t, inv);
+    }
+    tdone = t + 1;
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if (lane == 0) st_sc1u(w.strm, base | SW_ENDED | static_cast<unsigned long long>(tdone));
+  __syncthreads();  // the tail's first barrier
+  // the end is visible before the tail rewrites perm / pos (behind its second barrier)
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+}
+
+// Worker's LDS (the launch's dynamic region): the records.
+constexpr int WK_ROWS = 64;
+constexpr size_t WK_LDS = sizeof(double) * (PB * PB + PB) + sizeof(int) * 3 * PB;
+
+// Bounded poll of the progress word by a whole wave: until the launch's word
+// shows more than `have` records or the panel's end.  0 = budget spent.
+__device__ inline unsigned long long strm_wait(const unsigned long long *word, unsigned seq,
+                                               int have, uint64_t t0, unsigned budget) {
+  unsigned long long v;
+  for (;;) {
+    const unsigned long long x = ld_sc1u(word);
+    v = (static_cast<unsigned long long>(
+             __builtin_amdgcn_readfirstlane(static_cast<unsigned>(x >> 32)))
+         << 32) |
+        __builtin_amdgcn_readfirstlane(static_cast<unsigned>(x));
+    if (static_cast<unsigned>(v >> 32) == seq &&
+        ((v & (SW_ENDED | SW_NOSTREAM)) != 0ull || int(v & SW_STEPS) > have))
+      break;
+    if (__builtin_amdgcn_s_memrealtime() - t0 > budget) {
+      v = 0ull;
+      break;
+    }
+    __builtin_amdgcn_s_sleep(4);
+  }
+  // no load of the caller moves above the poll (the record loads are sc1)
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  return v;
+}
+
+// One wave (workgroup blockIdx.x >= 1 of the piv_sel_kernel launch).
+__device__ __forceinline__ void piv_stream_worker(int n, int k, PivWs w,
+                                                  const double *__restrict__ Hc, unsigned seq,
+                                                  unsigned budget, char *smem) {
+  double *lpl = reinterpret_cast<double *>(smem);        // PB x PB  pivots' L rows
+  double *pinv_s = lpl + PB * PB;                        // PB
+  int *prow_s = reinterpret_cast<int *>(pinv_s + PB);    // PB
+  int *poi_s = prow_s + PB, *pq_s = poi_s + PB;          // PB each
+  const int lane = threadIdx.x, c = int(blockIdx.x) - 1;
+  if (seq == 0u || budget == 0u) return;
+  const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
+  const unsigned long long hdr = strm_wait(w.strm, seq, -1, t0, budget);
+  if (hdr == 0ull || (hdr & SW_NOSTREAM) != 0ull) return;
+  const int ps = int((hdr >> 16) & 0xffffull);
+  if (ps + WK_ROWS * c >= n) return;
+  const int x0 = ps + WK_ROWS * c + lane;
+  const bool valid = x0 < n;
+  const int xc = valid ? x0 : n - 1;
+  const int rl = w.perm[xc];
+  const int r = valid ? rl : -1;  // -1: no pivot's row
+  const int oi = xc - ps;         // compact index in the panel's H_k (in range also when !valid)
+  double d = w.dsc[rl];
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  {  // the rows above are the panel-start ones only if the panel has not ended since
+    const unsigned long long x = ld_sc1u(w.strm);
+    const bool stale = static_cast<unsigned>(x >> 32) != seq || (x & SW_ENDED) != 0ull;
+    if (__builtin_amdgcn_readfirstlane(int(stale))) return;
+  }
+  double lr[PB];
+#pragma unroll
+  for (int l = 0; l < PB; ++l) lr[l] = 0.0;
+  bool done = false;
+  int pos = x0;
+  int have = 0;
+  for (;;) {
+    const unsigned long long pw = strm_wait(w.strm, seq, have, t0, budget);
+    if (pw == 0ull) return;  // budget spent: nothing written, the net fills the chunk
+    const int s = min(int(pw & SW_STEPS), PB);
+    if (s > have) {
+      // records have .. s - 1 to LDS
+      if (lane >= have && lane < s) {
+        const int pr = ld_sc1i(w.prow + lane), po = ld_sc1i(w.ppoi + lane), pq = ld_sc1i(w.pq + lane);
+        const double pi = ld_sc1d(w.pinv + lane);
+        prow_s[lane] = pr;
+        poi_s[lane] = min(max(po, 0), n - ps - 1);
+        pq_s[lane] = pq;
+        pinv_s[lane] = pi;
+      }
+      for (int e0 = have * PB; e0 < s * PB; e0 += 4 * 64) {
+        double v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int e = e0 + lane + 64 * u;
+          v[u] = e < s * PB ? ld_sc1d(w.Lpp + e) : 0.0;
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int e = e0 + lane + 64 * u;
+          if (e < s * PB) lpl[e] = v[u];
+        }
+      }
+      __syncthreads();  // one live wave: orders the LDS writes before the reads below
+      // the new steps' entries of the pivots' rows, all in flight together;
+      // lr[j] holds the gathered H_k entry until step j turns it into L
+#pragma unroll
+      for (int j = 0; j < PB; ++j)
+        if (j >= have && j < s) lr[j] = Hc[hk_at(poi_s[j], oi, n)];
+      // piv_fill_kernel's sequence, step by step
+#pragma unroll
+      for (int t = 0; t < PB; ++t) {
+        if (t >= have && t < s) {  // uniform
+          const double *lp = lpl + t * PB;
+          double v = lr[t];
+#pragma unroll
+          for (int l = 0; l < t; ++l) v = fma(-lr[l], lp[l], v);
+          const double lv = v * pinv_s[t];
+          const bool act = !done, isp = prow_s[t] == r;
+          lr[t] = act ? (isp ? lp[t] : lv) : 0.0;
+          d = (act & !isp) ? fma(-lv, lv, d) : d;
+          // dgeqp3's swap of positions i and q: the pivot to i, the row at i to q
+          const int i = ps + t, q = pq_s[t];
+          pos = (act & isp) ? i : ((pos == i) & (q != i)) ? q : pos;
+          done = done | (act & isp);
+          // L (row-major by row id) goes out four steps at a time while the
+          // selector steps on, so the panel's end has only LT and dsc left
+          if ((t & 3) == 3 && valid) {
+            double *dst = w.L + size_t(r) * k + ps + (t - 3);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) dst[u] = lr[t - 3 + u];
+          }
+        }
+      }
+      have = s;
+    }
+    if ((pw & SW_ENDED) != 0ull) break;
+  }
+  const int tn = have, ps2 = ps + tn;
+  if (tn <= 0) return;
+  if (valid) w.dsc[r] = d;
+#pragma unroll
+  for (int l = 0; l < PB; ++l) {
+    if (valid && pos >= ps2 && pos < n) w.LT[size_t(l) * n + (pos - ps2)] = lr[l];
+    if (valid && l >= (tn & ~3) && l < tn) w.L[size_t(r) * k + ps + l] = lr[l];  // the last 0 .. 3
+  }
+  if (lane == 0) {
+    w.fdone[c] = int(seq);
+    (void)__hip_atomic_fetch_add((pv_u64 *)(w.strm + 1), 1ull, __ATOMIC_RELAXED,
+                                 __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
 // One panel: candidate selection, then the panel's steps (pivot rows gathered
 // from the compacted H_k).
+// Workgroup 0 is the selector; with seq != 0 (the streamed fill, TG_PIV_STREAM)
+// workgroups 1.. are fill workers (piv_stream_worker), one wave each.
 __global__ __launch_bounds__(STH) void piv_sel_kernel(int n, int k, PivWs w,
-                                                      const double *__restrict__ Hc, int flev) {
+                                                      const double *__restrict__ Hc, int flev,
+                                                      unsigned seq, unsigned budget) {
   extern __shared__ int permL[];  // n: position -> row
+  if (blockIdx.x != 0) {  // uniform
+    if (threadIdx.x < 64)
+      piv_stream_worker(n, k, w, Hc, seq, budget, reinterpret_cast<char *>(permL));
+    return;
+  }
   __shared__ unsigned hist[HPAD];
   __shared__ int cand[SEL + 1];  // + trash slot for branch-free compaction
   __shared__ double2 rec[STH / 64];
@@ -792,7 +1086,10 @@ __global__ __launch_bounds__(STH) void piv_sel_kernel(int n, int k, PivWs w,
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int ps = w.sstate[0];
   if (ps >= k) {
-    if (tid == 0) w.sstate[1] = 0;
+    if (tid == 0) {
+      w.sstate[1] = 0;
+      if (seq != 0u) st_sc1u(w.strm, sw_word(seq, ps) | SW_NOSTREAM | SW_ENDED);
+    }
     return;
   }
   const int pe = min(ps + PB, k);
@@ -803,6 +1100,18 @@ __global__ __launch_bounds__(STH) void piv_sel_kernel(int n, int k, PivWs w,
                   : !lev_pays(n - ps, 1) ? NLEV - 1
                                          : min(max(w.sstate[SS_LEV], 0), NLEV - 1);
   const int nsel = SEL >> (NLEV - 1 - lev);
+  // streamed fill: below the widest level wave 4 stays on through the steps as
+  // the publisher.  The panel's header goes out now (one store, no wait), so
+  // the workers load their rows while the candidates are selected; a panel at
+  // the widest level steps on all eight waves and is not streamed.
+  const bool pub = seq != 0u && lev < NLEV - 1;
+  // strm[1] counts the chunks the workers complete (the net launch returns at
+  // once when that is all of them); zeroed by the publisher's wave, whose
+  // drains put the zero ahead of the end it publishes and so of every add
+  if (seq != 0u && tid == 4 * 64) {
+    st_sc1u(w.strm + 1, 0ull);
+    st_sc1u(w.strm, sw_word(seq, ps) | (pub ? 0ull : SW_NOSTREAM | SW_ENDED));
+  }
 #ifdef TG_SEL_PHASES
   uint64_t selt_last = 0;
 #endif
@@ -973,7 +1282,7 @@ __global__ __launch_bounds__(STH) void piv_sel_kernel(int n, int k, PivWs w,
   for (int q = 0; q < STH / 64; ++q) nset += scnt[q];
   bo = bp - ps;  // compact index of the step-0 pivot (positions unchanged so far)
   block_argmax_sel<STH / 64>(bv, bp, brow, bo, rec, reco);
-  SelPanel sp{n,   k,  ps, pe,    nset, bp,   brow, bo,   lev,  flev < 0,
+  SelPanel sp{n,   k,  ps, pe,    nset, bp,   brow, bo,   lev,  flev < 0, pub,
               tau, bv, dS, pS,    permL, cand, rec,  reco, lrow,
 #ifdef TG_SEL_PHASES
               selt_last
@@ -987,7 +1296,10 @@ __global__ __launch_bounds__(STH) void piv_sel_kernel(int n, int k, PivWs w,
   }
   // one wave per SIMD from here on: the other four leave (a workgroup
   // barrier counts the waves that have not ended)
-  if (wid >= 4) return;
+  if (wid >= 4) {
+    if (pub && wid == 4) sel_publish<4>(sp, w, seq);
+    return;
+  }
   if (lev == 1) sel_steps<4, 2>(sp, w, Hc);
   else sel_steps<4, 1>(sp, w, Hc);
 }
@@ -1081,17 +1393,19 @@ __device__ __forceinline__ void sel_steps(const SelPanel &sp, PivWs w,
         permL[i] = piv;
         permL[q] = a;
       }
-      w.prow[t] = piv;
+      if (!sp.pub) w.prow[t] = piv;
     }
     SELT(2)
     __syncthreads();
     SELT(3)
     // the pivot's sqrt / reciprocal after the barrier: their latency overlaps
     // the update's fma chains below, which need inv only at their end
-    const double ljj = sqrt(fmax(dpiv, 0.0));
-    const double inv = ljj > 0.0 ? 1.0 / ljj : 0.0;
-    if (tid == 0) w.pinv[t] = inv;
-    if (tid <= t) w.Lpp[t * PB + tid] = tid < t ? lrow[tid] : ljj;
+    double ljj, inv;
+    piv_scale(dpiv, ljj, inv);
+    if (!sp.pub) {  // uniform; a streamed panel's publisher wave stores the record
+      if (tid == 0) w.pinv[t] = inv;
+      if (tid <= t) w.Lpp[t * PB + tid] = tid < t ? lrow[tid] : ljj;
+    }
     double lrw[PB > 1 ? PB : 1];
 #pragma unroll
     for (int l = 0; l < t; ++l) lrw[l] = lrow[l];
@@ -1166,9 +1480,13 @@ __device__ __forceinline__ void sel_steps(const SelPanel &sp, PivWs w,
 // One thread per position x >= ps (row perm[x], compact index oidx[x - ps]
 // in the panel's H_k block Hc); rows pivoted in the panel (x < ps + tn) get
 // their L entries and no LT column.
+// seq != 0: the net behind a streamed panel (launch number seq).  A row whose
+// panel-start chunk (compact index / 64) a worker has marked is filled
+// already; the kernel fills the others, and a block with none returns.
 template <int FT>
 __global__ __launch_bounds__(FT) void piv_fill_kernel(int n, int k, PivWs w,
-                                                      const double *__restrict__ Hc) {
+                                                      const double *__restrict__ Hc,
+                                                      unsigned seq) {
   __shared__ double lpp[PB][PB + 1];
   __shared__ double pinv[PB];
   __shared__ int prow[PB], poi[PB];
@@ -1176,11 +1494,22 @@ __global__ __launch_bounds__(FT) void piv_fill_kernel(int n, int k, PivWs w,
   __shared__ int rst[FT];
   const int tid = threadIdx.x;
   const int tn = w.sstate[1];
+  const unsigned long long wdone = seq != 0u ? w.strm[1] : 0ull;
   if (tn <= 0) return;
   const int ps = w.sstate[0] - tn, ps2 = ps + tn;
-  for (int x = tid; x < PB * PB; x += FT) {
-    const int i = x / PB, l = x % PB;
-    lpp[i][l] = (i < tn && l <= i) ? w.Lpp[x] : 0.0;
+  if (seq != 0u && wdone == static_cast<unsigned long long>(tg::cdiv(n - ps, 64))) return;
+  const int x = ps + blockIdx.x * FT + tid;
+  const bool valid = x < n;  // no early exit: the L rows go out through LDS below
+  const int xc = valid ? x : n - 1;
+  const int r = w.perm[xc], oi = w.oidx[xc - ps];
+  bool todo = valid;
+  if (seq != 0u) {  // uniform
+    todo = valid && unsigned(w.fdone[oi >> 6]) != seq;
+    if (!__syncthreads_or(todo)) return;
+  }
+  for (int e = tid; e < PB * PB; e += FT) {
+    const int i = e / PB, l = e % PB;
+    lpp[i][l] = (i < tn && l <= i) ? w.Lpp[e] : 0.0;
   }
   if (tid < PB) {
     pinv[tid] = tid < tn ? w.pinv[tid] : 0.0;
@@ -1188,10 +1517,6 @@ __global__ __launch_bounds__(FT) void piv_fill_kernel(int n, int k, PivWs w,
     poi[tid] = tid < tn ? w.oidx[tid] : 0;  // pivot i sits at position ps + i
   }
   __syncthreads();
-  const int x = ps + blockIdx.x * FT + tid;
-  const bool valid = x < n;  // no early exit: the L rows go out through LDS below
-  const int xc = valid ? x : n - 1;
-  const int r = w.perm[xc], oi = w.oidx[xc - ps];
   double hv[PB];
 #pragma unroll
   for (int i = 0; i < PB; ++i) hv[i] = i < tn ? Hc[hk_at(poi[i], oi, n)] : 0.0;
@@ -1214,13 +1539,13 @@ __global__ __launch_bounds__(FT) void piv_fill_kernel(int n, int k, PivWs w,
     d = (act & !isp) ? fma(-lv, lv, d) : d;
     done = done | (act & isp);
   }
-  if (valid) w.dsc[r] = d;
+  if (todo) w.dsc[r] = d;
 #pragma unroll
   for (int l = 0; l < PB; ++l) {
-    if (valid && x >= ps2) w.LT[size_t(l) * n + (x - ps2)] = lr[l];
+    if (todo && x >= ps2) w.LT[size_t(l) * n + (x - ps2)] = lr[l];
     lst[tid][l] = lr[l];
   }
-  rst[tid] = valid ? r : -1;
+  rst[tid] = todo ? r : -1;
   __syncthreads();
   // L is row-major by row id (rows scattered): 32 lanes write one row's
   // panel segment contiguously instead of every lane striding k apart
@@ -1424,7 +1749,9 @@ __global__ __launch_bounds__(256) void piv_init2_kernel(int n, PivWs w) {
     w.dsc[j] = w.Hk[size_t(j) * n + j];
     w.perm[j] = j;
     w.pos[j] = j;
+    if (j < tg::cdiv(n, 64)) w.fdone[j] = 0;
   }
+  if (blockIdx.x == 0 && threadIdx.x < 2) w.strm[threadIdx.x] = 0ull;
   if (blockIdx.x == 0 && threadIdx.x < 16) w.sstate[threadIdx.x] = 0;
 }
 
@@ -1472,8 +1799,18 @@ static int pivot_core_sel(hipStream_t st, PivWs &w, int n, int k) {
 #endif
   hipLaunchKernelGGL(piv_init2_kernel, dim3(std::min(64, tg::cdiv(n, 256))), dim3(256), 0, st, n, w);
   TG_LAUNCHED();
-  const size_t lds = sizeof(int) * size_t((n + 1) & ~1) +
-                     (n <= SEL_LDS_N ? (sizeof(double) + sizeof(int)) * size_t(n) : 0);
+  // TG_PIV_STREAM=0: the fill as a launch of its own behind the steps
+  // (development switch, per call).  TG_PIV_STREAM_BUDGET: the workers' wait
+  // budget in ticks of the 100 MHz clock (default 2 ms; 0: every worker
+  // leaves at once and the net launch fills everything)
+  const char *sv = getenv("TG_PIV_STREAM");
+  const bool stream = !(sv && sv[0] == '0');
+  unsigned budget = 200000u;
+  if (const char *sb = getenv("TG_PIV_STREAM_BUDGET")) budget = unsigned(strtoul(sb, nullptr, 10));
+  unsigned seq = 0;  // launch number of a streamed panel (0: not streamed)
+  const size_t lds = std::max(sizeof(int) * size_t((n + 1) & ~1) +
+                                  (n <= SEL_LDS_N ? (sizeof(double) + sizeof(int)) * size_t(n) : 0),
+                              stream ? WK_LDS : size_t(0));
   if (lds > 48 * 1024)
     TG_HIP(hipFuncSetAttribute((const void *)piv_sel_kernel,
                                hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
@@ -1520,10 +1857,16 @@ static int pivot_core_sel(hipStream_t st, PivWs &w, int n, int k) {
       const int rows = n - (done + p);
       if (pend_rows > 0) TG_HIP(schur_compact(pend_rows));
       auto tok = tg::prof_begin(st, tg::PROF_PIVSTEP, 8.0 * double(n) * PB * 3, 0.0);
-      hipLaunchKernelGGL(piv_sel_kernel, dim3(1), dim3(STH), lds, st, n, k, w, hc, flev);
+      // streamed: one worker per 64-row chunk, at most one per remaining CU
+      // (chunks beyond that are the net launch's)
+      const int nwork = stream ? std::min(ncu - 1, tg::cdiv(rows, WK_ROWS)) : 0;
+      if (stream) ++seq;
+      hipLaunchKernelGGL(piv_sel_kernel, dim3(1 + nwork), dim3(STH), lds, st, n, k, w, hc, flev, seq,
+                         budget);
       // one wave per workgroup: the gathers of the pivots' columns spread
       // over 4x the CUs of 256-thread groups (n = 12,288: -1.4 ms per solve)
-      hipLaunchKernelGGL(piv_fill_kernel<64>, dim3(tg::cdiv(rows, 64)), dim3(64), 0, st, n, k, w, hc);
+      hipLaunchKernelGGL(piv_fill_kernel<64>, dim3(tg::cdiv(rows, 64)), dim3(64), 0, st, n, k, w, hc,
+                         seq);
       tg::prof_end(st, tok);
       TG_LAUNCHED();
       pend_rows = rows;
