@@ -1,5 +1,13 @@
-// Back-transformation Z <- Q1 Q2 Z for few eigenvectors (k <= 32 columns) in
-// ONE persistent launch.
+// Back-transformation of the two-stage eigensolver.  This file holds every
+// kernel that applies the bulge-chasing reflectors (Q2) -- the level-by-level
+// form for any k (q2_tfactor_kernel, q2_apply_kernel: sb_q2_tfactors,
+// sb_apply_q2, sb2st_t2_count; at the end of the file) and the few-vector
+// forms below -- and the few-vector Q1.  The level-by-level Q1 (sb_apply_q1)
+// is in band.hip, next to the forward reduction whose ytz_kernel and RowMap
+// it shares; the chase that writes the reflector records is in bulge.hip.
+//
+// Z <- Q1 Q2 Z for few eigenvectors (k <= 32 columns) in ONE persistent
+// launch.
 //
 // Second half of `torch.linalg.eigh` (/root/reference/src/TruncGPTQ/
 // gptq_utils.py:93) for the complement path's ~14 dropped eigenvectors.
@@ -30,6 +38,7 @@ namespace {
 
 using tg::SB_B;
 using tg::SB_C;
+using tg::ntasks;
 
 typedef double doublex4 __attribute__((ext_vector_type(4)));
 typedef double doublex2 __attribute__((ext_vector_type(2)));
@@ -77,7 +86,6 @@ union BtShared {
   SmQ1 q1;
 };
 
-__device__ inline int ntasks(int n, int j) { return (j <= n - 3) ? (n - 3 - j) / SB_B + 1 : 0; }
 __device__ inline bool refl_valid(int n, int j, int s) { return j <= n - 3 && s < ntasks(n, j); }
 
 // TG_BT_XCD=1: the workers are the workgroups that landed on the first XCD
@@ -1650,6 +1658,245 @@ hipError_t sb_apply_few(hipStream_t st, double *Z, const FewPlan &fp, const SbPl
     return few_flags(st, d, h, 2, timed_out);
   }
   return few_bt(st, Z, fp, pl, b, d, nlev2, timed_out);
+}
+
+}  // namespace tg
+
+// ---------------------------------------------------------------------------
+// Back-transformation Z <- Q2 Z, one launch per level (sb_apply_q2, any k).
+// Reflectors are grouped into blocks
+// (G2, s) = sweeps 32 G2 .. 32 G2 + 31 at step s: a staircase Y of 63 rows
+// (column a = reflector of sweep 32 G2 + a, rows a .. a + 31 of the block,
+// block rows start at 32 G2 + 1 + 32 s) with Q_block = H_0 H_1 ... H_31 =
+// I - Y T Y^T.  Valid order (== applying the reflectors in reverse): later
+// sweep groups first, steps ascending within a group; blocks overlap only
+// with (G2, s-1) and (G2+1 or later, s' < s + 1), so level
+// s + (NG2 - 1 - G2) is a set of row-disjoint blocks: one launch per level.
+// ---------------------------------------------------------------------------
+namespace {
+
+__global__ __launch_bounds__(256) void q2_tfactor_kernel(const double *__restrict__ V2, int n,
+                                                         int smax, double *__restrict__ T2) {
+  __shared__ double Vs[QB][SB_B];
+  __shared__ double Gs[QB][QB + 1];
+  __shared__ double Ts[QB][QB + 1];
+  __shared__ double taus[QB];
+  const int G2 = blockIdx.y, s = blockIdx.x, tid = threadIdx.x;
+  const int j0 = G2 * QB;
+  double *Tout = T2 + (int64_t(G2) * smax + s) * QB * QB;
+  if (!refl_valid(n, j0, s)) return;
+  for (int idx = tid; idx < QB * SB_B; idx += 256) {
+    const int a = idx / SB_B, i = idx % SB_B;
+    const bool ok = refl_valid(n, j0 + a, s);
+    const double x = ok ? V2[(int64_t(j0 + a) * smax + s) * SB_B + i] : 0.0;
+    Vs[a][i] = i == 0 ? (ok ? 1.0 : 0.0) : x;
+    if (i == 0) taus[a] = x;  // element 0 of the record is tau
+  }
+  __syncthreads();
+  for (int q = 0; q < 4; ++q) {
+    const int idx = tid + 256 * q, a = idx >> 5, c = idx & 31;
+    double g = 0.0;
+    if (a < c)
+      for (int i = c; i < a + SB_B; ++i) g += Vs[a][i - a] * Vs[c][i - c];
+    Gs[a][c] = g;
+    Ts[a][c] = 0.0;
+  }
+  __syncthreads();
+  // row a of T is independent of the other rows (dlarft forward columnwise):
+  // T[a][c] = -tau_c sum_{a<=e<c} T[a][e] G[e][c], T[a][a] = tau_a; thread a
+  // keeps its row in registers (no barrier per column).  The terms e < a are
+  // exact zeros, so the sums match the column-by-column order bit for bit.
+  if (tid < QB) {
+    double trow[QB];
+#pragma unroll
+    for (int c = 0; c < QB; ++c) {
+      double acc = 0.0;
+#pragma unroll
+      for (int e = 0; e < c; ++e) acc += trow[e] * Gs[e][c];
+      const double tc = taus[c];
+      trow[c] = tid < c ? -tc * acc : (tid == c ? tc : 0.0);
+    }
+#pragma unroll
+    for (int c = 0; c < QB; ++c) Ts[tid][c] = trow[c];
+  }
+  __syncthreads();
+  for (int idx = tid; idx < QB * QB; idx += 256) Tout[idx] = Ts[idx >> 5][idx & 31];
+}
+
+// One level: blockIdx.y enumerates the level's blocks, each wave one
+// 32-column slab of Z (n x k row-major) over the block's rows (64-row tile
+// in registers as eight 16x16 C-layout fragments).
+__global__ __launch_bounds__(256) void q2_apply_kernel(double *__restrict__ Z, int k, int n,
+                                                       const double *__restrict__ V2,
+                                                       const double *__restrict__ T2, int smax,
+                                                       int ng2, int level, int s_lo) {
+  const int s = s_lo + blockIdx.y;
+  const int G2 = ng2 - 1 - (level - s);
+  const int j0 = G2 * QB;
+  if (G2 < 0 || !refl_valid(n, j0, s)) return;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int lr = lane >> 4, lc = lane & 15;
+  const int c0 = (blockIdx.x * 4 + wid) * 32;
+  const int rb0 = j0 + 1 + s * SB_B;  // first row of the block
+  __shared__ double Vs[QB][SB_B + 1];
+  __shared__ double Ts[QB][QB + 1];
+  {
+    const double *Tb = T2 + (int64_t(G2) * smax + s) * QB * QB;
+    double vv[4], tt[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int idx = threadIdx.x + 256 * q, a = idx >> 5, d = idx & 31;
+      const int jj = refl_valid(n, j0 + a, s) ? j0 + a : j0;  // clamp to a valid reflector
+      vv[q] = V2[(int64_t(jj) * smax + s) * SB_B + d];
+      tt[q] = Tb[idx];
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int idx = threadIdx.x + 256 * q, a = idx >> 5, d = idx & 31;
+      Vs[a][d] = refl_valid(n, j0 + a, s) ? (d == 0 ? 1.0 : vv[q]) : 0.0;
+      Ts[a][d] = tt[q];
+    }
+  }
+  __syncthreads();
+  if (c0 >= k) return;
+  // Y[i][a] = v_a[i - a]  (rows past n hold zeros in v)
+  auto yval = [&](int i, int a) -> double {
+    const int d = i - a;
+    return (d >= 0 && d < SB_B) ? Vs[a][d] : 0.0;
+  };
+  doublex4 F[4][2];
+  {
+    double zl[4][4][2];
+#pragma unroll
+    for (int rb = 0; rb < 4; ++rb)
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb) {
+          const int row = min(rb0 + rb * 16 + lr + 4 * q, n - 1);
+          const int col = min(c0 + cb * 16 + lc, k - 1);
+          zl[rb][q][cb] = Z[int64_t(row) * k + col];
+        }
+#pragma unroll
+    for (int rb = 0; rb < 4; ++rb)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int i = rb * 16 + lr + 4 * q;
+        const bool ok = i < QR && rb0 + i < n;
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb)
+          F[rb][cb][q] = (ok && c0 + cb * 16 + lc < k) ? zl[rb][q][cb] : 0.0;
+      }
+  }
+  // P = Y^T Z  (32 x 32)
+  doublex4 Pa[2][2];
+#pragma unroll
+  for (int ia = 0; ia < 2; ++ia)
+#pragma unroll
+    for (int cb = 0; cb < 2; ++cb) Pa[ia][cb] = doublex4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+  for (int rb = 0; rb < 4; ++rb)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int i = rb * 16 + 4 * q + lr;
+      double ya[2];
+#pragma unroll
+      for (int ia = 0; ia < 2; ++ia) ya[ia] = yval(i, ia * 16 + lc);
+#pragma unroll
+      for (int ia = 0; ia < 2; ++ia)
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb)
+          Pa[ia][cb] = __builtin_amdgcn_mfma_f64_16x16x4f64(ya[ia], F[rb][cb][q], Pa[ia][cb], 0, 0, 0);
+    }
+  // M = T P   (T upper triangular 32 x 32); B operand of K-step (ia, q) = Pa[ia][cb][q]
+  doublex4 Ma[2][2];
+#pragma unroll
+  for (int ia = 0; ia < 2; ++ia)
+#pragma unroll
+    for (int cb = 0; cb < 2; ++cb) Ma[ia][cb] = doublex4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+  for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int kk = kb * 16 + 4 * q + lr;
+      double ta[2];
+#pragma unroll
+      for (int ia = 0; ia < 2; ++ia) ta[ia] = Ts[ia * 16 + lc][kk];
+#pragma unroll
+      for (int ia = 0; ia < 2; ++ia)
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb)
+          Ma[ia][cb] = __builtin_amdgcn_mfma_f64_16x16x4f64(ta[ia], Pa[kb][cb][q], Ma[ia][cb], 0, 0, 0);
+    }
+  // Z -= Y M
+#pragma unroll
+  for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int kk = kb * 16 + 4 * q + lr;
+#pragma unroll
+      for (int rb = 0; rb < 4; ++rb) {
+        const double ya = -yval(rb * 16 + lc, kk);
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb)
+          F[rb][cb] = __builtin_amdgcn_mfma_f64_16x16x4f64(ya, Ma[kb][cb][q], F[rb][cb], 0, 0, 0);
+      }
+    }
+#pragma unroll
+  for (int rb = 0; rb < 4; ++rb)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int i = rb * 16 + lr + 4 * q;
+      const int row = rb0 + i;
+      if (i >= QR || row >= n) continue;
+#pragma unroll
+      for (int cb = 0; cb < 2; ++cb) {
+        const int col = c0 + cb * 16 + lc;
+        if (col < k) Z[int64_t(row) * k + col] = F[rb][cb][q];
+      }
+    }
+}
+
+}  // namespace
+
+namespace tg {
+
+hipError_t sb_q2_tfactors(hipStream_t st, int n, const double *V2,
+                          double *T2) {
+  const int nsw = n - 2;
+  if (nsw <= 0) return hipSuccess;
+  hipLaunchKernelGGL(q2_tfactor_kernel, dim3(sb_smax(n), cdiv(nsw, QB)), dim3(256), 0, st, V2,
+                     n, sb_smax(n), T2);
+  return hipGetLastError();
+}
+
+hipError_t sb_apply_q2(hipStream_t st, int n, double *Z, int k, const double *V2,
+                       double *T2) {
+  const int nsw = n - 2;
+  if (nsw <= 0) return hipSuccess;
+  const int smax = sb_smax(n);
+  const int ng2 = cdiv(nsw, QB);
+  hipLaunchKernelGGL(q2_tfactor_kernel, dim3(smax, ng2), dim3(256), 0, st, V2, n, smax, T2);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return err;
+  const int nlev = smax + ng2 - 1;
+  for (int level = 0; level < nlev; ++level) {
+    const int s_lo = std::max(0, level - (ng2 - 1)), s_hi = std::min(smax - 1, level);
+    if (s_hi < s_lo) continue;
+    const double rows = double(s_hi - s_lo + 1) * QR;
+    auto tok = tg::prof_begin(st, tg::PROF_Q2, 16.0 * rows * k, 4.0 * rows * QB * k + 2.0 * QB * QB * k);
+    hipLaunchKernelGGL(q2_apply_kernel, dim3(cdiv(k, 128), s_hi - s_lo + 1), dim3(256), 0, st, Z,
+                       k, n, V2, T2, smax, ng2, level, s_lo);
+    tg::prof_end(st, tok);
+    err = hipGetLastError();
+    if (err != hipSuccess) return err;
+  }
+  return hipSuccess;
+}
+
+size_t sb2st_t2_count(int n) {
+  const int nsw = std::max(1, n - 2);
+  return size_t(cdiv(nsw, QB)) * sb_smax(n) * QB * QB;
 }
 
 }  // namespace tg

@@ -1,8 +1,14 @@
-// Stage 1 of the two-stage symmetric eigensolver: full -> band reduction
-// (sy2sb) with TSQR panel factorisations, and its back-transformation.
+// The two-stage symmetric eigensolver's stages, shared constants and
+// workspace layout:
+//   band.hip    stage 1, full -> band (sy2sb, TSQR or panel-QR panels), and
+//               its level-by-level back-transformation sb_apply_q1;
+//   pqr.hip     the panel QR of stage 1;
+//   bulge.hip   stage 2, band -> tridiagonal by bulge chasing (sb2st) with
+//               the tridiagonal guard;
+//   backtr.hip  the back-transformation Q2 (sb_apply_q2, sb_q2_tfactors) and
+//               the few-vector Q1 Q2 (few_plan, sb_apply_few).
 #pragma once
 #include <algorithm>
-#include <type_traits>
 #include <vector>
 
 #include "common.h"
@@ -47,7 +53,7 @@ struct SbBufs {
   double *Gr, *U;         // gathered rows / symmetric update (ncmax*32 x n)
   double *Xs;             // gathered rows of X (ncmax*32 x ncmax*32)
   double *Zg, *P, *Mz;    // back-transformation temporaries (ncmax*32 x k)
-  // stage 2 (bulge.hip)
+  // stage 2 (bulge.hip; T2 by backtr.hip)
   double *Bst;            // band storage n x 2b
   double *V2;             // bulge-chasing reflector records (tau, v_1..v_{b-1}), (n-2) x smax x b
   double *T2;             // Q2 block T factors
@@ -66,6 +72,11 @@ hipError_t panel_qr(hipStream_t st, double *A, int lda, int p, int r0, int m, do
                     double *YT, double *T, double *part, double *bc, unsigned *cnt,
                     unsigned *tmo);
 
+// Tasks of sweep j of the bulge chase (reflectors of b rows from row j + 1
+// down); sb_smax = the tasks of sweep 0, at least 1.
+__host__ __device__ inline int ntasks(int n, int j) {
+  return (j <= n - 3) ? (n - 3 - j) / SB_B + 1 : 0;
+}
 int sb_smax(int n);
 size_t sb2st_prog_words(int n);
 size_t sb2st_t2_count(int n);
@@ -86,10 +97,7 @@ void sb_layout(A &ar, int n, int kmax, const SbPlan &pl, SbBufs *bp) {
   SbBufs d{};
   SbBufs &b = bp ? *bp : d;
   const size_t w = size_t(pl.ncmax) * SB_B;
-  auto take = [&](double *&dst, size_t cnt) {
-    if constexpr (std::is_same_v<A, Arena>) dst = ar.template take<double>(cnt);
-    else ar.template take<double>(cnt);
-  };
+  auto take = [&](double *&dst, size_t cnt) { dst = ar.template take<double>(cnt); };
   take(b.Y, pl.ytotal + 1);
   take(b.T, pl.ttotal + 1);
   take(b.YT, size_t(n) * SB_B);
@@ -114,17 +122,14 @@ void sb_layout(A &ar, int n, int kmax, const SbPlan &pl, SbBufs *bp) {
   take(b.V2, nsw * smax * SB_B);
   take(b.T2, sb2st_t2_count(n));
   // per-group progress + 4 control words (XCD, group queue, stall flag)
-  if constexpr (std::is_same_v<A, Arena>) b.prog = ar.template take<unsigned>(sb2st_prog_words(n));
-  else ar.template take<unsigned>(sb2st_prog_words(n));
+  b.prog = ar.template take<unsigned>(sb2st_prog_words(n));
   // partials: panel QR (2 per worker), X row blocks, M (one per 128 rows)
   const size_t npart = std::max<size_t>(std::max<size_t>(2 * PQR_NWMAX + 2, size_t(n) / SB_C + 2),
                                         size_t(n) / 128 + 2) * 1024;
   take(b.pq_part, npart);
   take(b.pq_bc, PQR_BC_DOUBLES);
-  if constexpr (std::is_same_v<A, Arena>) b.pq_ctl = ar.template take<unsigned>(pq_ctl_words(n));
-  else ar.template take<unsigned>(pq_ctl_words(n));
-  if constexpr (std::is_same_v<A, Arena>) b.xm_tick = ar.template take<unsigned>(xm_tick_words(n));
-  else ar.template take<unsigned>(xm_tick_words(n));
+  b.pq_ctl = ar.template take<unsigned>(pq_ctl_words(n));
+  b.xm_tick = ar.template take<unsigned>(xm_tick_words(n));
   take(b.xm_xpart, xm_xpart_doubles(n));
 }
 

@@ -30,6 +30,7 @@
 
 #include "band.h"
 #include "gemm64.h"
+#include "lanes.h"
 #include "reduce.h"
 #include "spin.h"
 
@@ -100,66 +101,19 @@ struct RowMap {
   }
 };
 
-// Cross-lane exchange without the LDS crossbar: partner value of `x` for
-// the pairings lane^32, lane^16 (v_permlane{32,16}_swap), lane^15 (DPP
-// row_mirror), lane^7 (row_half_mirror), lane^3, lane^1 (quad_perm).
-// Each pairing flips a new bit (32, 16, 8 via 15, 4 via 7, 2 via 3, 1), so a
-// butterfly over them in this order is a full reduction / reduce-scatter.
-// Half-wave sums without selects: v_permlane{32,16}_swap(x, x) leaves the
-// lower half's x in one register and the upper half's in the other, lane
-// aligned, so their sum is x[l] + x[l ^ 32] (x[l] + x[l ^ 16]) in every lane.
-__device__ inline double hsum32(double x) {
-  const int lo = __double2loint(x), hi = __double2hiint(x);
-  const auto l = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-  const auto h = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-  return __hiloint2double(h[0], l[0]) + __hiloint2double(h[1], l[1]);
-}
-__device__ inline double hsum16(double x) {
-  const int lo = __double2loint(x), hi = __double2hiint(x);
-  const auto l = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-  const auto h = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-  return __hiloint2double(h[0], l[0]) + __hiloint2double(h[1], l[1]);
-}
-template <int CTRL>
-__device__ inline double xdpp(double x) {
-  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(x), CTRL, 0xF, 0xF, false);
-  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(x), CTRL, 0xF, 0xF, false);
-  return __hiloint2double(hi, lo);
-}
-constexpr int DPP_MIRROR = 0x140, DPP_HALF_MIRROR = 0x141, DPP_XOR3 = 0x1B, DPP_XOR1 = 0xB1;
-
 __device__ inline double rcp_nr(double x) {
   double r = __builtin_amdgcn_rcp(x);
   r = fma(fma(-x, r, 1.0), r, r);
   return fma(fma(-x, r, 1.0), r, r);
 }
 
-// Reduce-scatter of the 32 products v * r[l] over the wave: lane ends with
-// the sum of column rs_col(lane) (bits 5..1 of the lane id pick the half kept
-// at each step).
-__device__ inline int rs_col(int lane) {
-  return ((lane >> 5) & 1) * 16 + ((lane >> 4) & 1) * 8 + ((lane >> 3) & 1) * 4 +
-         ((lane >> 2) & 1) * 2 + ((lane >> 1) & 1);
-}
-// q_l = v0 r0[l] + v1 r1[l], formed inside the first step.
-// Swap-based reduce-scatter step: v_permlane{32,16}_swap(a, b) exchanges the
-// upper half of `a` with the lower half of `b` (lanes 32-63 / odd 16-lane
-// rows), so afterwards one register holds both halves' `a` values and the
-// other both halves' `b` values, lane-aligned: their sum is the pairwise
-// sum of `a` in the lower half and of `b` in the upper half -- no selects.
-__device__ inline double rs_swap32(double a, double b) {
-  const auto l = __builtin_amdgcn_permlane32_swap(__double2loint(a), __double2loint(b), false, false);
-  const auto h = __builtin_amdgcn_permlane32_swap(__double2hiint(a), __double2hiint(b), false, false);
-  return __hiloint2double(h[0], l[0]) + __hiloint2double(h[1], l[1]);
-}
-__device__ inline double rs_swap16(double a, double b) {
-  const auto l = __builtin_amdgcn_permlane16_swap(__double2loint(a), __double2loint(b), false, false);
-  const auto h = __builtin_amdgcn_permlane16_swap(__double2hiint(a), __double2hiint(b), false, false);
-  return __hiloint2double(h[0], l[0]) + __hiloint2double(h[1], l[1]);
-}
-
+// Reduce-scatter of the 32 products q_l = v0 r0[l] + v1 r1[l] over the wave,
+// formed inside the first step: lane ends with the sum of column
+// tg::lanes::rs_col(lane).  The two-array form of tg::lanes::reduce_scatter32,
+// on the same swaps and DPP pairings (lanes.h).
 __device__ inline double reduce_scatter32(const double (&r0)[32], const double (&r1)[32],
                                           double v0, double v1, int lane) {
+  using namespace tg::lanes;
   auto qf = [&](int l) { return v0 * r0[l] + v1 * r1[l]; };
   double p[16];
   // lanes 0-31 keep column k, lanes 32-63 column k + 16
@@ -234,7 +188,7 @@ __global__ __launch_bounds__(QT) void tsqr_qr_kernel(const double *__restrict__ 
   load_row(tid, r0);
   load_row(tid + QT, r1);
   for (int idx = tid; idx < SB_B * (SB_B + 1); idx += QT) (&Ts[0][0])[idx] = 0.0;
-  const int mycol = rs_col(lane);
+  const int mycol = tg::lanes::rs_col(lane);
   // One reduction per column: with the raw column x as weights,
   // d_l = sum_{i>j} x_i P[i][l] gives both the squared norm (l = j) and,
   // since v = (x_i scal)_{i>j} with v_j = 1, every v^T P[:, l] =

@@ -1,5 +1,10 @@
 // Stage 2 of the two-stage eigensolver: band (half-bandwidth b = SB_B) ->
-// symmetric tridiagonal by bulge chasing, plus the back-transformation Q2.
+// symmetric tridiagonal by bulge chasing.  This file holds the two chase
+// kernels (bulge_df_kernel, the default, and the step-synchronous
+// bulge_lds_kernel, TG_BULGE_DF=0, its bit-exact oracle), the tridiagonal
+// guard, sb2st() and the stage's C ABI (tg_band_tridiag).  The
+// back-transformation that applies the reflector records written here (Q2) is
+// in backtr.hip.
 //
 // Second half of the reduction inside `torch.linalg.eigh`
 // (/root/reference/src/TruncGPTQ/gptq_utils.py:92).  Algorithm (one column
@@ -23,16 +28,14 @@
 // holds tau in element 0 (v_0 = 1 is implicit) and v_1 .. v_{b-1} after it,
 // written as one 256-B line pair of 16-B stores.
 #include <algorithm>
-#include <type_traits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
-#include <unistd.h>
 
 #include "../../include/truncgptq.h"
 #include "band.h"
 #include "common.h"
+#include "lanes.h"
 #include "spin.h"
 
 namespace {
@@ -40,41 +43,9 @@ namespace {
 using tg::SB_B;
 constexpr int LDB = 2 * SB_B;
 
-// Half-wave sums without selects: v_permlane{32,16}_swap(x, x) leaves the
-// lower half's x in one register and the upper half's in the other, lane
-// aligned, so their sum is x[l] + x[l ^ 32] (x[l] + x[l ^ 16]) in every lane.
-__device__ inline double hsum32(double x) {
-  const int lo = __double2loint(x), hi = __double2hiint(x);
-  const auto l = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-  const auto h = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-  return __hiloint2double(h[0], l[0]) + __hiloint2double(h[1], l[1]);
-}
-__device__ inline double hsum16(double x) {
-  const int lo = __double2loint(x), hi = __double2hiint(x);
-  const auto l = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-  const auto h = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-  return __hiloint2double(h[0], l[0]) + __hiloint2double(h[1], l[1]);
-}
-template <int CTRL>
-__device__ inline double xdpp(double x) {
-  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(x), CTRL, 0xF, 0xF, false);
-  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(x), CTRL, 0xF, 0xF, false);
-  return __hiloint2double(hi, lo);
-}
-// Full wave sum in every lane without the LDS crossbar: pairings lane^32,
-// lane^16 (permlane swaps), lane^15 / lane^7 (DPP row mirrors), lane^3,
-// lane^1 (quad_perm) flip a new bit each.
-__device__ inline double wsum(double s) {
-  s = hsum32(s);
-  s = hsum16(s);
-  s += xdpp<0x140>(s);
-  s += xdpp<0x141>(s);
-  s += xdpp<0x1B>(s);
-  s += xdpp<0xB1>(s);
-  return s;
-}
-
-__device__ inline int ntasks(int n, int j) { return (j <= n - 3) ? (n - 3 - j) / SB_B + 1 : 0; }
+using tg::lanes::hsum32;
+using tg::lanes::wsum;
+using tg::ntasks;
 
 // ---------------------------------------------------------------------------
 // LDS-resident pipeline.  A workgroup owns G_SW consecutive sweeps; at step t
@@ -88,8 +59,7 @@ __device__ inline int ntasks(int n, int j) { return (j <= n - 3) ? (n - 3 - j) /
 // columns are in memory):
 //   producer (writer wave): plain 16-B stores of the retired columns ->
 //     s_waitcnt vmcnt(0) (every store acknowledged by the XCD's L2) ->
-//     progress store (TG_BULGE_FLAG_L2=1: plain `sc0` store, the line stays
-//     in that L2; 0: relaxed agent `sc1` store, written through);
+//     progress store (plain `sc0` store, the line stays in that L2);
 //   consumer (loader wave): relaxed agent `sc1` poll of prog[G-1] (L1
 //     bypassed) until it covers the columns of the next step, then `sc1`
 //     16-B buffer loads of those columns (L1 bypassed, served by the L2).
@@ -116,12 +86,6 @@ __device__ inline int ntasks(int n, int j) { return (j <= n - 3) ? (n - 3 - j) /
 // ---------------------------------------------------------------------------
 #ifndef TG_BULGE_GSW
 #define TG_BULGE_GSW 2
-#endif
-#ifndef TG_BULGE_FLAG_L2
-#define TG_BULGE_FLAG_L2 1
-#endif
-#ifndef TG_BULGE_SPLIT
-#define TG_BULGE_SPLIT 3  // bit 0: wave 0 takes half of the write-back; bit 1: wave 3 half of the load
 #endif
 #ifndef TG_BULGE_STATS
 #define TG_BULGE_STATS 0  // per-step s_memrealtime stamps (build-time: they slow every step)
@@ -401,33 +365,13 @@ __device__ __forceinline__ unsigned *lane0_or_dummy(unsigned *real, unsigned *du
 }
 
 __device__ __forceinline__ void publish(unsigned *p, unsigned v) {
-#if TG_BULGE_FLAG_L2
   __hip_atomic_store((tg::spin_u32 *)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#else
-  tg::ctl_store(p, v);
-#endif
 }
 
 #if TG_BULGE_STATS
 #define BSTAMP(v) const uint64_t v = __builtin_amdgcn_s_memrealtime();
 #else
 #define BSTAMP(v)
-#endif
-#ifndef TG_BULGE_HB
-#define TG_BULGE_HB 0  // debug: per-wave heartbeat (group, step, phase) into host memory
-#endif
-#if TG_BULGE_HB
-// record (group, step, live lanes, phase) from the first active lane
-#define HB(ph)                                                                          \
-  {                                                                                     \
-    const unsigned long long ex_ = __builtin_amdgcn_read_exec();                        \
-    if (int(__lane_id()) == __builtin_ctzll(ex_))                                       \
-      ((volatile unsigned long long *)stats)[blockIdx.x * 16 + wid] =                   \
-          (unsigned long long)(G + 1) << 32 | (unsigned long long)(t + 1) << 16 |       \
-          (unsigned long long)__builtin_popcountll(ex_) << 8 | (ph);                    \
-  }
-#else
-#define HB(ph)
 #endif
 
 // ctl[0] = chosen XCD + 1, ctl[1] = group queue, ctl[2] = stall word
@@ -473,8 +417,7 @@ __global__ __launch_bounds__(BT) void bulge_lds_kernel(double *__restrict__ B, i
   constexpr int NTC = LDB / 2;            // 16-B chunks per column
   constexpr int PFN = SB_B * NTC / BT + 1;  // chunks per thread of a whole-workgroup load
   // halves of each step's write-back (NH) and load (NHL), 1 KB blocks by parity
-  constexpr int NH = (TG_BULGE_SPLIT & 1) ? 2 : 1;
-  constexpr int NHL = (TG_BULGE_SPLIT & 2) ? 2 : 1;
+  constexpr int NH = 2, NHL = 2;
   constexpr int NBLK = SB_B * NTC / 64;  // 1 KB blocks per step's load
   constexpr int PW = NBLK / NHL;         // blocks (chunks per lane) of one load half
   unsigned nstep = 0;  // steps this workgroup has run over all its groups (sh_wdone's clock)
@@ -545,14 +488,12 @@ __global__ __launch_bounds__(BT) void bulge_lds_kernel(double *__restrict__ B, i
     __syncthreads();
     for (int t = 0; t < total; ++t) {
       BSTAMP(c0t)
-      HB(1)
       // Transfers of step t, each split in NH halves (64-chunk blocks by parity):
       // write-back of the columns step t-1 retired (drained, then the last half
       // to drain publishes t) and the load of the columns step t+1 adds (after
       // the producer's progress covers them).  One wave moves ~16 KB per
-      // ~1.5 us, so with TG_BULGE_SPLIT the left-block waves (the lightest
-      // tasks) take the second halves: wave 0 stores before its task, wave 3
-      // loads after its task.
+      // ~1.5 us, so the left-block waves (the lightest tasks) take the second
+      // halves: wave 0 stores before its task, wave 3 loads after its task.
       auto wb_issue = [&](int half) {
         const int nl = group_low(n, nsw, j0, g, t);
         // wave-uniform trip count (scalar loop), the tail masked by an if
@@ -570,19 +511,15 @@ __global__ __launch_bounds__(BT) void bulge_lds_kernel(double *__restrict__ B, i
       };
       auto wb_finish = [&](int half) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if constexpr (NH == 1) {
+        // each half marks its word, then reads the other's: LDS serves one
+        // CU's requests in order, so the later of the two sees both marks
+        // (both publishing the same step is harmless)
+        __hip_atomic_store(&sh_wdone[half], nstep + 1, __ATOMIC_SEQ_CST,
+                           __HIP_MEMORY_SCOPE_WORKGROUP);
+        const unsigned o = __hip_atomic_load(&sh_wdone[half ^ 1], __ATOMIC_SEQ_CST,
+                                             __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (__builtin_amdgcn_readfirstlane(o) >= nstep + 1)
           publish(lane0_or_dummy(prog + G, dummy, wlane), unsigned(t));
-        } else {
-          // each half marks its word, then reads the other's: LDS serves one
-          // CU's requests in order, so the later of the two sees both marks
-          // (both publishing the same step is harmless)
-          __hip_atomic_store(&sh_wdone[half], nstep + 1, __ATOMIC_SEQ_CST,
-                             __HIP_MEMORY_SCOPE_WORKGROUP);
-          const unsigned o = __hip_atomic_load(&sh_wdone[half ^ 1], __ATOMIC_SEQ_CST,
-                                               __HIP_MEMORY_SCOPE_WORKGROUP);
-          if (__builtin_amdgcn_readfirstlane(o) >= nstep + 1)
-            publish(lane0_or_dummy(prog + G, dummy, wlane), unsigned(t));
-        }
       };
       // the load as two parts (issue after the poll; LDS writes once the data is in)
       auto load_issue = [&](int half, double2 (&buf)[PW]) -> bool {
@@ -590,10 +527,8 @@ __global__ __launch_bounds__(BT) void bulge_lds_kernel(double *__restrict__ B, i
         if (!(t + 1 < total && nh > ld)) return false;
         const unsigned need = unsigned(min(group_need(t + 1), ptotal + 1));
         if (known < need) {
-          HB(4)
           // the column loads below issue after the poll has returned
           known = max(need, wait_wave(need));
-          HB(5)
         }
 #pragma unroll
         for (int u = 0; u < PW; ++u) {
@@ -616,7 +551,6 @@ __global__ __launch_bounds__(BT) void bulge_lds_kernel(double *__restrict__ B, i
             R[rslot(c)][2 * h + 1] = buf[u].y;
           }
         }
-        HB(10)
       };
       auto load_half = [&](int half) {
         double2 buf[PW];
@@ -625,35 +559,30 @@ __global__ __launch_bounds__(BT) void bulge_lds_kernel(double *__restrict__ B, i
       if (wid < NCW) {
         const int pair = wid / 3, role = wid % 3;
         const int s = t - LAG * pair;
-        if (NH == 2 && wid == 0) wb_issue(1);
+        if (wid == 0) wb_issue(1);
         if (pair < g && s >= 0 && s < ntasks(n, j0 + pair)) {
           const int jj = j0 + pair, r1 = jj + 1 + s * SB_B;
           const bool nx = s + 1 < ntasks(n, jj);
           const Refl &ri = rfl[pair][t & 1];
           Refl &ro = rfl[pair][(t + 1) & 1];
-          HB(6)
           if (r1 >= SB_B && r1 + 2 * SB_B <= n)
             bulge_task_lds<true>(R, n, jj, s, role, nx, V2, smax, wsc[wid], ri, ro);
           else
             bulge_task_lds<false>(R, n, jj, s, role, nx, V2, smax, wsc[wid], ri, ro);
-          HB(7)
         } else if (pair < g && pair > 0 && s == -1 && role == 2) {
           first_refl(R, n, j0 + pair, rfl[pair][(t + 1) & 1]);
         }
-        if (NH == 2 && wid == 0) wb_finish(1);
-        if (NHL == 2 && wid == 3) load_half(1);
+        if (wid == 0) wb_finish(1);
+        if (wid == 3) load_half(1);
       } else if (wid == NCW) {
         // writer: retire the columns step t-1 left behind, drain, publish t
         wb_issue(0);
-        HB(8)
         wb_finish(0);
-        HB(9)
       } else {
         // loader: the columns step t + 1 adds
         load_half(0);
       }
       BSTAMP(c1t)
-      HB(2)
       __syncthreads();
       ++nstep;
       if (t + 1 < total) ld = max(ld, group_high(n, j0, t + 1));
@@ -737,15 +666,6 @@ constexpr int DNCW = 3 * DG;          // role waves
 #ifndef TG_BULGE_DF_XF
 #define TG_BULGE_DF_XF 1
 #endif
-// 1: the loader issues a chunk's loads before it waits for ring space (the
-// space is needed only by the LDS write).  Measured 69.0 -> 68.4 ms at n =
-// 12,288 with a relaxed poll; with an ordered poll 69.1 ms, no gain, and it
-// was the order that exposed the round-5 race, so the default is 0 (loads
-// after the ring-space wait)
-#ifndef TG_BULGE_LD_EARLY
-#define TG_BULGE_LD_EARLY 0
-#endif
-
 constexpr int DXF = TG_BULGE_DF_XF;           // loader waves = writer waves (each moves 1/DXF)
 constexpr int DBT = 64 * (DNCW + 2 * DXF);    // + loaders + writers
 // ring span at the tightest spacing: the loader's chunk ahead of sweep 0
@@ -938,19 +858,12 @@ struct DfSync {
 // flight; the difference is that the compiler now knows the order, which the
 // round-5 race (a relaxed poll, the loader's ring writes scheduled above it)
 // showed it did not (tools/check_handoff_isa.py checks the lowering).
-// TG_BULGE_RACE_DEMO=1 (build-time, tools/bulge_hunt.py only): the round-5
-// relaxed form, to show the tridiagonal guard catching the race it allowed.
-#ifndef TG_BULGE_RACE_DEMO
-#define TG_BULGE_RACE_DEMO 0
-#endif
-constexpr int LDS_ACQ = TG_BULGE_RACE_DEMO ? __ATOMIC_RELAXED : __ATOMIC_ACQUIRE;
-constexpr int LDS_REL = TG_BULGE_RACE_DEMO ? __ATOMIC_RELAXED : __ATOMIC_RELEASE;
 __device__ __forceinline__ unsigned lds_get(const unsigned *p) {
-  return __builtin_amdgcn_readfirstlane(__hip_atomic_load(p, LDS_ACQ, __HIP_MEMORY_SCOPE_WORKGROUP));
+  return __builtin_amdgcn_readfirstlane(
+      __hip_atomic_load(p, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP));
 }
 __device__ __forceinline__ void lds_put(unsigned *p, unsigned v) {
-  if constexpr (TG_BULGE_RACE_DEMO) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __hip_atomic_store(p, v, LDS_REL, __HIP_MEMORY_SCOPE_WORKGROUP);
+  __hip_atomic_store(p, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
 #if TG_BULGE_STATS
@@ -1164,9 +1077,7 @@ __global__ __launch_bounds__(DBT) void bulge_df_kernel(double *__restrict__ B, i
         if (G > 0 && !lds_get(&sy.dead) && !tg::spin_geq(prog + G - 1, unsigned(ce), stall, timeout))
           lds_put(&sy.dead, 1u);
         DF_ACC(0)
-#if !TG_BULGE_LD_EARLY
         df_wait(&sy.wbs, unsigned(max(0, ce - RING)), sy, stall, timeout);
-#endif
         DF_ACC(1)
         double2 buf[PL];
 #pragma unroll
@@ -1177,11 +1088,6 @@ __global__ __launch_bounds__(DBT) void bulge_df_kernel(double *__restrict__ B, i
           buf[u] = make_double2(__builtin_bit_cast(double, u32x2{v4[0], v4[1]}),
                                 __builtin_bit_cast(double, u32x2{v4[2], v4[3]}));
         }
-#if TG_BULGE_LD_EARLY
-        // the ring space is needed only by the LDS write: the chunk's loads
-        // are in flight while the writer retires the slots
-        df_wait(&sy.wbs, unsigned(max(0, ce - RING)), sy, stall, timeout);
-#endif
 #if TG_BULGE_STATS
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         DF_ACC(2)
@@ -1419,11 +1325,109 @@ __global__ void extract_tri_kernel(const double *__restrict__ Bst, int n,
   e[i] = bad ? __builtin_nan("") : (i + 1 < n) ? Bst[int64_t(i) * LDB + 1] : 0.0;
 }
 
+// TG_BULGE_STATS (environment, read per call): the elapsed time of the chase
+// launch on stderr; a -DTG_BULGE_STATS=1 build adds the kernels' clock stamps
+// (`buf`, their stats argument) and, with TG_BULGE_TRACE, the role end times
+// of the traced groups.  begin() and end() bracket the launch; with the
+// variable unset they do nothing and `buf` stays null.
+struct BulgeStats {
+  hipStream_t st;
+  const bool want = getenv("TG_BULGE_STATS") != nullptr;
+  unsigned long long *buf = nullptr;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  explicit BulgeStats(hipStream_t s) : st(s) {}
+  BulgeStats(const BulgeStats &) = delete;
+  BulgeStats &operator=(const BulgeStats &) = delete;
+  ~BulgeStats() {
+    if (buf) (void)hipFree(buf);
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+  }
+  void begin() {
+    if (!want) return;
+    if (TG_BULGE_STATS) {
+      const size_t ns = 128 + 3 * 4 * 4 * 128;
+      (void)hipMalloc(&buf, ns * sizeof(unsigned long long));
+      (void)hipMemsetAsync(buf, 0, ns * sizeof(unsigned long long), st);
+    }
+    (void)hipEventCreate(&e0);
+    (void)hipEventCreate(&e1);
+    (void)hipEventRecord(e0, st);
+  }
+  // df: the dataflow kernel ran (its stamps have another layout)
+  void end(bool df) {
+    if (!want) return;
+    (void)hipEventRecord(e1, st);
+    unsigned long long h[128] = {0};
+    if (buf) (void)hipMemcpyAsync(h, buf, sizeof(h), hipMemcpyDeviceToHost, st);
+    (void)hipStreamSynchronize(st);
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, e0, e1);
+    fprintf(stderr, "bulge: %.2f ms (%s, G_SW %d)\n", ms, df ? "dataflow" : "step", df ? DG : G_SW);
+    if (!buf) return;
+    if (df) {
+      print_trace();
+      print_dataflow(h);
+    } else {
+      print_step(h);
+    }
+  }
+  // role end times (us, relative) of tasks 0..15 of the traced groups
+  void print_trace() const {
+#if TG_BULGE_STATS
+    if (!getenv("TG_BULGE_TRACE")) return;
+    static unsigned long long tr[3 * 4 * DG * 128];
+    (void)hipMemcpy(tr, buf + 128, sizeof(tr), hipMemcpyDeviceToHost);
+    unsigned long long t0 = ~0ull;
+    for (auto x : tr) if (x && x < t0) t0 = x;
+    const char *rn[4] = {"A", "D", "G", "L"};
+    for (int gg = 0; gg < 3; ++gg)
+      for (int r = 0; r < 4; ++r)
+        for (int q = 0; q < (r == 3 ? 1 : DG); ++q) {
+          fprintf(stderr, "  trace G%d %s%d:", DF_TR0 + gg, rn[r], q);
+          for (int t = 0; t < 16; ++t) {
+            const unsigned long long x = tr[(gg * 4 + r) * DG * 128 + q * 128 + t];
+            fprintf(stderr, " %6.2f", x ? (x - t0) / 100.0 : -1.0);
+          }
+          fprintf(stderr, "\n");
+        }
+#endif
+  }
+  static void print_dataflow(const unsigned long long (&h)[128]) {
+    const double W = double(h[0] ? h[0] : 1);
+    fprintf(stderr, "  workers %llu, worker time %.1f us; per wave and worker (us): "
+            "[t0 t1 t2 t3 t4] count; per unit (us)\n"
+            "  (tasks: own refl/slot, prev sweep/loader, task; loader: producer, ring, "
+            "issue->data, LDS+publish; writer: idle, LDS read, store issue, drain, publish)\n",
+            h[0], h[5] / 100.0 / W);
+    for (int w = 0; w < DNCW + 2 * DXF; ++w) {
+      const unsigned long long *x = h + 8 + 6 * w;
+      const double c = double(x[5] ? x[5] : 1);
+      fprintf(stderr, "   w%d %s: %.0f %.0f %.0f %.0f %.0f  %llu;  %.2f %.2f %.2f %.2f %.2f\n", w,
+              w < DNCW ? (w % 3 == 0 ? "A" : w % 3 == 1 ? "D" : "G")
+                       : (w < DNCW + DXF ? "load" : "write"),
+              x[0] / 100.0 / W, x[1] / 100.0 / W, x[2] / 100.0 / W, x[3] / 100.0 / W,
+              x[4] / 100.0 / W, x[5], x[0] / 100.0 / c, x[1] / 100.0 / c, x[2] / 100.0 / c,
+              x[3] / 100.0 / c, x[4] / 100.0 / c);
+    }
+  }
+  static void print_step(const unsigned long long (&h)[128]) {
+    const double W = double(h[0]), S = double(h[6]);
+    fprintf(stderr,
+            "  workers %.0f, steps/worker %.0f; per step (us): wait %.2f task %.2f bar %.2f\n",
+            W, S / W, h[1] / 100.0 / S, h[2] / 100.0 / S, h[3] / 100.0 / S);
+    if (h[5]) fprintf(stderr, "  shader clock %.2f GHz\n", 0.1 * double(h[4]) / double(h[5]));
+    fprintf(stderr, "  per-wave busy per step (us):");
+    for (int w = 0; w < NCW + 2; ++w) fprintf(stderr, " w%d %.2f", w, h[8 + w] / 100.0 / S);
+    fprintf(stderr, "\n");
+  }
+};
+
 }  // namespace
 
 namespace tg {
 
-int sb_smax(int n) { return n >= 3 ? (n - 3) / SB_B + 1 : 1; }
+int sb_smax(int n) { return std::max(1, ntasks(n, 0)); }
 
 // progress word per sweep group (at most one group per sweep, whichever
 // kernel runs) + control words + 64 dummy words; the control words start at
@@ -1449,6 +1453,7 @@ static bool guard_on() {
 
 hipError_t sb2st(hipStream_t st, const double *A, int lda, int n, double *Bst, double *V2,
                  unsigned *prog, double *d, double *e) {
+  // 1. the band, in bulge-chasing storage
   hipLaunchKernelGGL(extract_band_kernel, dim3(cdiv(int64_t(n) * LDB, 256)), dim3(256), 0, st, A,
                      int64_t(lda), n, Bst);
   hipError_t err = hipGetLastError();
@@ -1456,153 +1461,52 @@ hipError_t sb2st(hipStream_t st, const double *A, int lda, int n, double *Bst, d
   const int nsw = n - 2;
   const unsigned *stall = nullptr;
   if (nsw > 0) {
-    const bool df = bulge_dataflow();
+    const bool df = bulge_dataflow(), guard = guard_on();
     err = hipMemsetAsync(prog, 0, sizeof(unsigned) * sb2st_prog_words(n), st);
     if (err != hipSuccess) return err;
+    unsigned *ctl = prog + nsw;  // [0] XCD + 1, [1] group queue, [2] stall flag, [3] guard word
+    stall = ctl + 2;
     double *gpart = reinterpret_cast<double *>(prog + guard_off(n));
-    if (guard_on()) {
+    // 2. the guard's sums over the band
+    if (guard) {
       hipLaunchKernelGGL(band_inv_kernel, dim3(GINV), dim3(256), 0, st, Bst, n, gpart);
       err = hipGetLastError();
       if (err != hipSuccess) return err;
     }
-    unsigned *ctl = prog + nsw;  // [0] XCD + 1, [1] group queue, [2] stall flag
-    stall = ctl + 2;
+    // 3. the chase.  ~12.3 kflop per task (3 blocks of b x b, rank-1 each),
+    // n^2/(2b) tasks; band streamed once per sweep group (load + write-back,
+    // L2-resident).  One workgroup per CU (the ring fills the LDS): the
+    // elected XCD's share of the grid is its CUs, the other XCDs' workgroups
+    // exit at once
     const unsigned long long timeout = spin_timeout_ticks("TG_BULGE_TIMEOUT_TICKS");
-    // TG_BULGE_STATS (environment): elapsed time of the launch; with a
-    // -DTG_BULGE_STATS=1 build also the per-step clock stamps per wave
-    const bool want = getenv("TG_BULGE_STATS") != nullptr;
-    unsigned long long *stats = nullptr;
-#if TG_BULGE_HB
-    unsigned long long *hbh = nullptr;
-    (void)hipHostMalloc(&hbh, 256 * 16 * 8, hipHostMallocMapped);
-    memset(hbh, 0, 256 * 16 * 8);
-    (void)hipHostGetDevicePointer((void **)&stats, hbh, 0);
-    hipEvent_t hbe;
-    (void)hipEventCreateWithFlags(&hbe, hipEventDisableTiming);
-#endif
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (want) {
-      if (TG_BULGE_STATS) {
-        const size_t ns = 128 + 3 * 4 * 4 * 128;
-        (void)hipMalloc(&stats, ns * sizeof(unsigned long long));
-        (void)hipMemsetAsync(stats, 0, ns * sizeof(unsigned long long), st);
-      }
-      (void)hipEventCreate(&e0);
-      (void)hipEventCreate(&e1);
-      (void)hipEventRecord(e0, st);
-    }
-    // ~12.3 kflop per task (3 blocks of b x b, rank-1 each), n^2/(2b) tasks;
-    // band streamed once per sweep group (load + write-back, L2-resident)
     double ntask = 0.0;
-    for (int j = 0; j < nsw; ++j) ntask += (n - 3 - j) / SB_B + 1;
+    for (int j = 0; j < nsw; ++j) ntask += ntasks(n, j);
+    const XcdInfo xi = xcd_info();
+    BulgeStats stats(st);
+    stats.begin();
     auto tok = tg::prof_begin(st, tg::PROF_BULGE, 8.0 * LDB * double(n) * n / (df ? DG : G_SW),
                               12.0 * SB_B * SB_B * ntask);
-    // one workgroup per CU (the ring fills the LDS): the elected XCD's share
-    // of the grid is its CUs, the other XCDs' workgroups exit at once
-    const XcdInfo xi = xcd_info();
     if (df)
       hipLaunchKernelGGL(bulge_df_kernel, dim3(xi.xcds * xi.cus_per_xcd), dim3(DBT), 0, st, Bst,
-                         n, V2, sb_smax(n), prog, ctl, stats, timeout);
+                         n, V2, sb_smax(n), prog, ctl, stats.buf, timeout);
     else
       hipLaunchKernelGGL(bulge_lds_kernel, dim3(xi.xcds * xi.cus_per_xcd), dim3(BT), 0, st, Bst,
-                         n, V2, sb_smax(n), prog, ctl, stats, timeout);
+                         n, V2, sb_smax(n), prog, ctl, stats.buf, timeout);
     tg::prof_end(st, tok);
     err = hipGetLastError();
     if (err != hipSuccess) return err;
-#if TG_BULGE_HB
-    (void)hipEventRecord(hbe, st);
-    for (int it = 0; it < 300 && hipEventQuery(hbe) == hipErrorNotReady; ++it) usleep(10000);
-    if (hipEventQuery(hbe) == hipErrorNotReady) {
-      fprintf(stderr, "bulge HANG: heartbeat (block: wave=G/step/lanes/phase)\n");
-      for (int bk = 0; bk < 256; ++bk) {
-        bool any = false;
-        for (int w = 0; w < NCW + 2; ++w) any |= hbh[bk * 16 + w] != 0;
-        if (!any) continue;
-        fprintf(stderr, "  b%3d:", bk);
-        for (int w = 0; w < NCW + 2; ++w) {
-          const unsigned long long v = hbh[bk * 16 + w];
-          fprintf(stderr, " %llu/%llu/%llu/%llu", (v >> 32) - 1, ((v >> 16) & 0xffff) - 1, (v >> 8) & 255,
-                  v & 255);
-        }
-        fprintf(stderr, "\n");
-      }
-      fflush(stderr);
-      _exit(3);
-    }
-    stats = nullptr;
-#endif
-    if (want) {
-      (void)hipEventRecord(e1, st);
-      unsigned long long h[128] = {0};
-      if (stats) (void)hipMemcpyAsync(h, stats, sizeof(h), hipMemcpyDeviceToHost, st);
-      (void)hipStreamSynchronize(st);
-      float ms = 0.f;
-      (void)hipEventElapsedTime(&ms, e0, e1);
-      fprintf(stderr, "bulge: %.2f ms (%s, G_SW %d)\n", ms, df ? "dataflow" : "step", df ? DG : G_SW);
-#if TG_BULGE_STATS
-      if (stats && df && getenv("TG_BULGE_TRACE")) {
-        // role end times (us, relative) of tasks 0..15 of the traced groups
-        static unsigned long long tr[3 * 4 * DG * 128];
-        (void)hipMemcpy(tr, stats + 128, sizeof(tr), hipMemcpyDeviceToHost);
-        unsigned long long t0 = ~0ull;
-        for (auto x : tr) if (x && x < t0) t0 = x;
-        const char *rn[4] = {"A", "D", "G", "L"};
-        for (int gg = 0; gg < 3; ++gg)
-          for (int r = 0; r < 4; ++r)
-            for (int q = 0; q < (r == 3 ? 1 : DG); ++q) {
-              fprintf(stderr, "  trace G%d %s%d:", DF_TR0 + gg, rn[r], q);
-              for (int t = 0; t < 16; ++t) {
-                const unsigned long long x = tr[(gg * 4 + r) * DG * 128 + q * 128 + t];
-                fprintf(stderr, " %6.2f", x ? (x - t0) / 100.0 : -1.0);
-              }
-              fprintf(stderr, "\n");
-            }
-      }
-#endif
-      if (stats && df) {
-        const double W = double(h[0] ? h[0] : 1);
-        fprintf(stderr, "  workers %llu, worker time %.1f us; per wave and worker (us): "
-                "[t0 t1 t2 t3 t4] count; per unit (us)\n"
-                "  (tasks: own refl/slot, prev sweep/loader, task; loader: producer, ring, "
-                "issue->data, LDS+publish; writer: idle, LDS read, store issue, drain, publish)\n",
-                h[0], h[5] / 100.0 / W);
-        for (int w = 0; w < DNCW + 2 * DXF; ++w) {
-          const unsigned long long *x = h + 8 + 6 * w;
-          const double c = double(x[5] ? x[5] : 1);
-          fprintf(stderr, "   w%d %s: %.0f %.0f %.0f %.0f %.0f  %llu;  %.2f %.2f %.2f %.2f %.2f\n", w,
-                  w < DNCW ? (w % 3 == 0 ? "A" : w % 3 == 1 ? "D" : "G")
-                           : (w < DNCW + DXF ? "load" : "write"),
-                  x[0] / 100.0 / W, x[1] / 100.0 / W, x[2] / 100.0 / W, x[3] / 100.0 / W,
-                  x[4] / 100.0 / W, x[5], x[0] / 100.0 / c, x[1] / 100.0 / c, x[2] / 100.0 / c,
-                  x[3] / 100.0 / c, x[4] / 100.0 / c);
-        }
-        (void)hipFree(stats);
-        stats = nullptr;
-      }
-      if (stats) {
-        const double W = double(h[0]), S = double(h[6]);
-        fprintf(stderr,
-                "  workers %.0f, steps/worker %.0f; per step (us): wait %.2f task %.2f bar %.2f\n",
-                W, S / W, h[1] / 100.0 / S, h[2] / 100.0 / S, h[3] / 100.0 / S);
-        if (h[5]) fprintf(stderr, "  shader clock %.2f GHz\n", 0.1 * double(h[4]) / double(h[5]));
-        fprintf(stderr, "  per-wave busy per step (us):");
-        for (int w = 0; w < NCW + 2; ++w) fprintf(stderr, " w%d %.2f", w, h[8 + w] / 100.0 / S);
-        fprintf(stderr, "\n");
-        (void)hipFree(stats);
-      }
-      (void)hipEventDestroy(e0);
-      (void)hipEventDestroy(e1);
+    stats.end(df);
+    // 4. the guard's check of the tridiagonal against those sums
+    if (guard) {
+      const char *cx = getenv("TG_TRI_GUARD_CORRUPT");  // tests: corrupt one d before the check
+      hipLaunchKernelGGL(tri_check_kernel, dim3(1), dim3(256), 0, st, Bst, n, gpart,
+                         cx ? atoi(cx) : -1, getenv("TG_TRI_GUARD_NOPOISON") ? 1 : 0,
+                         gpart + 2 * GINV, ctl + 3);
+      err = hipGetLastError();
+      if (err != hipSuccess) return err;
     }
   }
-  if (nsw > 0 && guard_on()) {
-    const char *cx = getenv("TG_TRI_GUARD_CORRUPT");  // tests: corrupt one d before the check
-    double *gpart = reinterpret_cast<double *>(prog + guard_off(n));
-    hipLaunchKernelGGL(tri_check_kernel, dim3(1), dim3(256), 0, st, Bst, n, gpart,
-                       cx ? atoi(cx) : -1, getenv("TG_TRI_GUARD_NOPOISON") ? 1 : 0,
-                       gpart + 2 * GINV, prog + nsw + 3);
-    err = hipGetLastError();
-    if (err != hipSuccess) return err;
-  }
+  // 5. (d, e), or NaN after a stall or a guard violation
   hipLaunchKernelGGL(extract_tri_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, Bst, n, stall, d,
                      e);
   return hipGetLastError();
@@ -1634,250 +1538,6 @@ hipError_t sb2st_stalled(hipStream_t st, int n, const unsigned *prog, bool *stal
 }  // namespace tg
 
 // ---------------------------------------------------------------------------
-// Back-transformation Z <- Q2 Z.  Reflectors are grouped into blocks
-// (G2, s) = sweeps 32 G2 .. 32 G2 + 31 at step s: a staircase Y of 63 rows
-// (column a = reflector of sweep 32 G2 + a, rows a .. a + 31 of the block,
-// block rows start at 32 G2 + 1 + 32 s) with Q_block = H_0 H_1 ... H_31 =
-// I - Y T Y^T.  Valid order (== applying the reflectors in reverse): later
-// sweep groups first, steps ascending within a group; blocks overlap only
-// with (G2, s-1) and (G2+1 or later, s' < s + 1), so level
-// s + (NG2 - 1 - G2) is a set of row-disjoint blocks: one launch per level.
-// ---------------------------------------------------------------------------
-namespace {
-
-typedef double doublex4 __attribute__((ext_vector_type(4)));
-constexpr int QB = 32;           // sweeps per block (= SB_B)
-constexpr int QR = QB + SB_B - 1;  // rows per block (63)
-
-__device__ inline bool refl_valid(int n, int j, int s) { return j <= n - 3 && s < ntasks(n, j); }
-
-__global__ __launch_bounds__(256) void q2_tfactor_kernel(const double *__restrict__ V2, int n,
-                                                         int smax, double *__restrict__ T2) {
-  __shared__ double Vs[QB][SB_B];
-  __shared__ double Gs[QB][QB + 1];
-  __shared__ double Ts[QB][QB + 1];
-  __shared__ double taus[QB];
-  const int G2 = blockIdx.y, s = blockIdx.x, tid = threadIdx.x;
-  const int j0 = G2 * QB;
-  double *Tout = T2 + (int64_t(G2) * smax + s) * QB * QB;
-  if (!refl_valid(n, j0, s)) return;
-  for (int idx = tid; idx < QB * SB_B; idx += 256) {
-    const int a = idx / SB_B, i = idx % SB_B;
-    const bool ok = refl_valid(n, j0 + a, s);
-    const double x = ok ? V2[(int64_t(j0 + a) * smax + s) * SB_B + i] : 0.0;
-    Vs[a][i] = i == 0 ? (ok ? 1.0 : 0.0) : x;
-    if (i == 0) taus[a] = x;  // element 0 of the record is tau
-  }
-  __syncthreads();
-  for (int q = 0; q < 4; ++q) {
-    const int idx = tid + 256 * q, a = idx >> 5, c = idx & 31;
-    double g = 0.0;
-    if (a < c)
-      for (int i = c; i < a + SB_B; ++i) g += Vs[a][i - a] * Vs[c][i - c];
-    Gs[a][c] = g;
-    Ts[a][c] = 0.0;
-  }
-  __syncthreads();
-  // row a of T is independent of the other rows (dlarft forward columnwise):
-  // T[a][c] = -tau_c sum_{a<=e<c} T[a][e] G[e][c], T[a][a] = tau_a; thread a
-  // keeps its row in registers (no barrier per column).  The terms e < a are
-  // exact zeros, so the sums match the column-by-column order bit for bit.
-  if (tid < QB) {
-    double trow[QB];
-#pragma unroll
-    for (int c = 0; c < QB; ++c) {
-      double acc = 0.0;
-#pragma unroll
-      for (int e = 0; e < c; ++e) acc += trow[e] * Gs[e][c];
-      const double tc = taus[c];
-      trow[c] = tid < c ? -tc * acc : (tid == c ? tc : 0.0);
-    }
-#pragma unroll
-    for (int c = 0; c < QB; ++c) Ts[tid][c] = trow[c];
-  }
-  __syncthreads();
-  for (int idx = tid; idx < QB * QB; idx += 256) Tout[idx] = Ts[idx >> 5][idx & 31];
-}
-
-// One level: blockIdx.y enumerates the level's blocks, each wave one
-// 32-column slab of Z (n x k row-major) over the block's rows (64-row tile
-// in registers as eight 16x16 C-layout fragments).
-__global__ __launch_bounds__(256) void q2_apply_kernel(double *__restrict__ Z, int k, int n,
-                                                       const double *__restrict__ V2,
-                                                       const double *__restrict__ T2, int smax,
-                                                       int ng2, int level, int s_lo) {
-  const int s = s_lo + blockIdx.y;
-  const int G2 = ng2 - 1 - (level - s);
-  const int j0 = G2 * QB;
-  if (G2 < 0 || !refl_valid(n, j0, s)) return;
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int lr = lane >> 4, lc = lane & 15;
-  const int c0 = (blockIdx.x * 4 + wid) * 32;
-  const int rb0 = j0 + 1 + s * SB_B;  // first row of the block
-  __shared__ double Vs[QB][SB_B + 1];
-  __shared__ double Ts[QB][QB + 1];
-  {
-    const double *Tb = T2 + (int64_t(G2) * smax + s) * QB * QB;
-    double vv[4], tt[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int idx = threadIdx.x + 256 * q, a = idx >> 5, d = idx & 31;
-      const int jj = refl_valid(n, j0 + a, s) ? j0 + a : j0;  // clamp to a valid reflector
-      vv[q] = V2[(int64_t(jj) * smax + s) * SB_B + d];
-      tt[q] = Tb[idx];
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int idx = threadIdx.x + 256 * q, a = idx >> 5, d = idx & 31;
-      Vs[a][d] = refl_valid(n, j0 + a, s) ? (d == 0 ? 1.0 : vv[q]) : 0.0;
-      Ts[a][d] = tt[q];
-    }
-  }
-  __syncthreads();
-  if (c0 >= k) return;
-  // Y[i][a] = v_a[i - a]  (rows past n hold zeros in v)
-  auto yval = [&](int i, int a) -> double {
-    const int d = i - a;
-    return (d >= 0 && d < SB_B) ? Vs[a][d] : 0.0;
-  };
-  doublex4 F[4][2];
-  {
-    double zl[4][4][2];
-#pragma unroll
-    for (int rb = 0; rb < 4; ++rb)
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int cb = 0; cb < 2; ++cb) {
-          const int row = min(rb0 + rb * 16 + lr + 4 * q, n - 1);
-          const int col = min(c0 + cb * 16 + lc, k - 1);
-          zl[rb][q][cb] = Z[int64_t(row) * k + col];
-        }
-#pragma unroll
-    for (int rb = 0; rb < 4; ++rb)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int i = rb * 16 + lr + 4 * q;
-        const bool ok = i < QR && rb0 + i < n;
-#pragma unroll
-        for (int cb = 0; cb < 2; ++cb)
-          F[rb][cb][q] = (ok && c0 + cb * 16 + lc < k) ? zl[rb][q][cb] : 0.0;
-      }
-  }
-  // P = Y^T Z  (32 x 32)
-  doublex4 Pa[2][2];
-#pragma unroll
-  for (int ia = 0; ia < 2; ++ia)
-#pragma unroll
-    for (int cb = 0; cb < 2; ++cb) Pa[ia][cb] = doublex4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-  for (int rb = 0; rb < 4; ++rb)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int i = rb * 16 + 4 * q + lr;
-      double ya[2];
-#pragma unroll
-      for (int ia = 0; ia < 2; ++ia) ya[ia] = yval(i, ia * 16 + lc);
-#pragma unroll
-      for (int ia = 0; ia < 2; ++ia)
-#pragma unroll
-        for (int cb = 0; cb < 2; ++cb)
-          Pa[ia][cb] = __builtin_amdgcn_mfma_f64_16x16x4f64(ya[ia], F[rb][cb][q], Pa[ia][cb], 0, 0, 0);
-    }
-  // M = T P   (T upper triangular 32 x 32); B operand of K-step (ia, q) = Pa[ia][cb][q]
-  doublex4 Ma[2][2];
-#pragma unroll
-  for (int ia = 0; ia < 2; ++ia)
-#pragma unroll
-    for (int cb = 0; cb < 2; ++cb) Ma[ia][cb] = doublex4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-  for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int kk = kb * 16 + 4 * q + lr;
-      double ta[2];
-#pragma unroll
-      for (int ia = 0; ia < 2; ++ia) ta[ia] = Ts[ia * 16 + lc][kk];
-#pragma unroll
-      for (int ia = 0; ia < 2; ++ia)
-#pragma unroll
-        for (int cb = 0; cb < 2; ++cb)
-          Ma[ia][cb] = __builtin_amdgcn_mfma_f64_16x16x4f64(ta[ia], Pa[kb][cb][q], Ma[ia][cb], 0, 0, 0);
-    }
-  // Z -= Y M
-#pragma unroll
-  for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int kk = kb * 16 + 4 * q + lr;
-#pragma unroll
-      for (int rb = 0; rb < 4; ++rb) {
-        const double ya = -yval(rb * 16 + lc, kk);
-#pragma unroll
-        for (int cb = 0; cb < 2; ++cb)
-          F[rb][cb] = __builtin_amdgcn_mfma_f64_16x16x4f64(ya, Ma[kb][cb][q], F[rb][cb], 0, 0, 0);
-      }
-    }
-#pragma unroll
-  for (int rb = 0; rb < 4; ++rb)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int i = rb * 16 + lr + 4 * q;
-      const int row = rb0 + i;
-      if (i >= QR || row >= n) continue;
-#pragma unroll
-      for (int cb = 0; cb < 2; ++cb) {
-        const int col = c0 + cb * 16 + lc;
-        if (col < k) Z[int64_t(row) * k + col] = F[rb][cb][q];
-      }
-    }
-}
-
-}  // namespace
-
-namespace tg {
-
-hipError_t sb_q2_tfactors(hipStream_t st, int n, const double *V2,
-                          double *T2) {
-  const int nsw = n - 2;
-  if (nsw <= 0) return hipSuccess;
-  hipLaunchKernelGGL(q2_tfactor_kernel, dim3(sb_smax(n), cdiv(nsw, QB)), dim3(256), 0, st, V2,
-                     n, sb_smax(n), T2);
-  return hipGetLastError();
-}
-
-hipError_t sb_apply_q2(hipStream_t st, int n, double *Z, int k, const double *V2,
-                       double *T2) {
-  const int nsw = n - 2;
-  if (nsw <= 0) return hipSuccess;
-  const int smax = sb_smax(n);
-  const int ng2 = cdiv(nsw, QB);
-  hipLaunchKernelGGL(q2_tfactor_kernel, dim3(smax, ng2), dim3(256), 0, st, V2, n, smax, T2);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return err;
-  const int nlev = smax + ng2 - 1;
-  for (int level = 0; level < nlev; ++level) {
-    const int s_lo = std::max(0, level - (ng2 - 1)), s_hi = std::min(smax - 1, level);
-    if (s_hi < s_lo) continue;
-    const double rows = double(s_hi - s_lo + 1) * QR;
-    auto tok = tg::prof_begin(st, tg::PROF_Q2, 16.0 * rows * k, 4.0 * rows * QB * k + 2.0 * QB * QB * k);
-    hipLaunchKernelGGL(q2_apply_kernel, dim3(cdiv(k, 128), s_hi - s_lo + 1), dim3(256), 0, st, Z,
-                       k, n, V2, T2, smax, ng2, level, s_lo);
-    tg::prof_end(st, tok);
-    err = hipGetLastError();
-    if (err != hipSuccess) return err;
-  }
-  return hipSuccess;
-}
-
-size_t sb2st_t2_count(int n) {
-  const int nsw = std::max(1, n - 2);
-  return size_t(cdiv(nsw, QB)) * sb_smax(n) * QB * QB;
-}
-
-}  // namespace tg
-
-// ---------------------------------------------------------------------------
 // C ABI: the band -> tridiagonal stage on its own (tests and tools).
 // ---------------------------------------------------------------------------
 namespace {
@@ -1890,16 +1550,9 @@ void band_ws_layout(A &ar, int n, BandWs *p) {
   BandWs d{};
   BandWs &b = p ? *p : d;
   const size_t nsw = size_t(std::max(1, n - 2)), smax = size_t(tg::sb_smax(n));
-  if constexpr (std::is_same_v<A, tg::Arena>) {
-    b.Bst = ar.template take<double>(size_t(n) * LDB);
-    b.V2 = ar.template take<double>(nsw * smax * SB_B);
-    b.prog = ar.template take<unsigned>(tg::sb2st_prog_words(n));
-  } else {
-    ar.template take<double>(size_t(n) * LDB);
-    ar.template take<double>(nsw * smax * SB_B);
-    ar.template take<double>(nsw * smax);
-    ar.template take<unsigned>(tg::sb2st_prog_words(n));
-  }
+  b.Bst = ar.template take<double>(size_t(n) * LDB);
+  b.V2 = ar.template take<double>(nsw * smax * SB_B);
+  b.prog = ar.template take<unsigned>(tg::sb2st_prog_words(n));
 }
 }  // namespace
 

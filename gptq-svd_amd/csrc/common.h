@@ -34,17 +34,20 @@ struct Arena {
   bool ok() const { return off <= cap; }
 };
 
-// Same layout arithmetic without a base pointer (for *_workspace_size()).
+// Same layout arithmetic without a base pointer (for *_workspace_size()):
+// the takes return null, so one layout function assigns for both.
 struct Sizer {
   size_t off = 0;
   template <class T>
-  void take(size_t count) {
+  T *take(size_t count) {
     off = (off + 255) & ~size_t(255);
     off += count * sizeof(T);
+    return nullptr;
   }
   template <class T>
-  void take_aligned(size_t count, size_t A) {
+  T *take_aligned(size_t count, size_t A) {
     off += A - 1 + count * sizeof(T);
+    return nullptr;
   }
 };
 

@@ -96,8 +96,7 @@ void tri_layout(A &ar, int n, Tri *t) {
   const int nblk = tg::cdiv(n, BT);
   auto take = [&](auto *&dst, size_t cnt) {
     using T = std::remove_reference_t<decltype(*dst)>;
-    if constexpr (std::is_same_v<A, tg::Arena>) dst = ar.template take<T>(cnt);
-    else ar.template take<T>(cnt);
+    dst = ar.template take<T>(cnt);
   };
   take(q.V, nn);
   take(q.PT, size_t(3) * NB * n);

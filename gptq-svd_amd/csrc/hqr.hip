@@ -251,8 +251,7 @@ void hqr_layout(Ar &ar, int k, HqrWs *w) {
   const size_t nb = size_t(tg::cdiv(k, HR));
   auto t = [&](auto *&dst, size_t cnt) {
     using T = std::remove_reference_t<decltype(*dst)>;
-    if constexpr (std::is_same_v<Ar, tg::Arena>) dst = ar.template take<T>(cnt);
-    else ar.template take<T>(cnt);
+    dst = ar.template take<T>(cnt);
   };
   t(q.V, size_t(k) * HB);
   t(q.T, nb * HB * HB);

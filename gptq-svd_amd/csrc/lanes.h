@@ -34,6 +34,34 @@ __device__ inline double rs_swap16(double a, double b) {
   return __hiloint2double(h[0], l[0]) + __hiloint2double(h[1], l[1]);
 }
 
+// Half-wave sums without selects: v_permlane{32,16}_swap(x, x) leaves the
+// lower half's x in one register and the upper half's in the other, lane
+// aligned, so their sum is x[l] + x[l ^ 32] (x[l] + x[l ^ 16]) in every lane.
+__device__ inline double hsum32(double x) {
+  const int lo = __double2loint(x), hi = __double2hiint(x);
+  const auto l = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
+  const auto h = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+  return __hiloint2double(h[0], l[0]) + __hiloint2double(h[1], l[1]);
+}
+__device__ inline double hsum16(double x) {
+  const int lo = __double2loint(x), hi = __double2hiint(x);
+  const auto l = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
+  const auto h = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+  return __hiloint2double(h[0], l[0]) + __hiloint2double(h[1], l[1]);
+}
+// Full wave sum in every lane: pairings lane^32, lane^16 (permlane swaps),
+// lane^15 / lane^7 (DPP row mirrors), lane^3, lane^1 (quad_perm) flip a new
+// bit each.
+__device__ inline double wsum(double s) {
+  s = hsum32(s);
+  s = hsum16(s);
+  s += xdpp<DPP_MIRROR>(s);
+  s += xdpp<DPP_HALF_MIRROR>(s);
+  s += xdpp<DPP_XOR3>(s);
+  s += xdpp<DPP_XOR1>(s);
+  return s;
+}
+
 // Column whose wave sum a lane holds after reduce_scatter32 (lanes l and
 // l ^ 1 hold the same column).
 __device__ inline int rs_col(int lane) {

@@ -19,7 +19,6 @@
 //   gram = 0, m > p    K = M^T M (p x p) with eigenpairs (mu, P),
 //                      Q = M P mu^-1/2.
 #include <algorithm>
-#include <type_traits>
 
 #include "../../include/truncgptq.h"
 #include "common.h"
@@ -166,18 +165,9 @@ void lrc_layout(A &ar, int m, int n, int p, int r, int gram, LrcBufs *b) {
                             size_t(re) * n,                     // B0
                             size_t(r)};                         // sc
   double *ptrs[9] = {};
-  for (int i = 0; i < 9; ++i) {
-    if constexpr (std::is_same_v<A, tg::Arena>)
-      ptrs[i] = ar.template take<double>(counts[i]);
-    else
-      ar.template take<double>(counts[i]);
-  }
+  for (int i = 0; i < 9; ++i) ptrs[i] = ar.template take<double>(counts[i]);
   const size_t eb = tg_eigh_workspace_size(q);
-  char *ep = nullptr;
-  if constexpr (std::is_same_v<A, tg::Arena>)
-    ep = ar.template take<char>(eb);
-  else
-    ar.template take<char>(eb);
+  char *ep = ar.template take<char>(eb);
   if (b) *b = LrcBufs{ptrs[0], ptrs[1], ptrs[2], ptrs[3], ptrs[4], ptrs[5], ptrs[6], ptrs[7],
                       ptrs[8], ep, eb};
 }

@@ -14,8 +14,6 @@
 // (deterministic).  The gathers W[:, perm] and (W - Wq)[:, perm] are one
 // streaming pass that writes both permuted operands (the GEMM then reads
 // K-contiguous rows), R_x is converted to FP32 on the fly in the B loads.
-#include <type_traits>
-
 #include "../../include/truncgptq.h"
 #include "common.h"
 
@@ -191,15 +189,9 @@ __global__ __launch_bounds__(64) void metric_sum_kernel(const double *__restrict
 template <class A>
 void metric_layout(A &ar, int m, int n, int k, float **Wp, float **Dp, double **part) {
   const int64_t nb = int64_t(tg::cdiv(m, TM)) * tg::cdiv(k, TN);
-  if constexpr (std::is_same_v<A, tg::Arena>) {
-    *Wp = ar.template take<float>(size_t(m) * n);
-    *Dp = ar.template take<float>(size_t(m) * n);
-    *part = ar.template take<double>(size_t(2 * nb));
-  } else {
-    ar.template take<float>(size_t(m) * n);
-    ar.template take<float>(size_t(m) * n);
-    ar.template take<double>(size_t(2 * nb));
-  }
+  *Wp = ar.template take<float>(size_t(m) * n);
+  *Dp = ar.template take<float>(size_t(m) * n);
+  *part = ar.template take<double>(size_t(2 * nb));
 }
 
 }  // namespace
@@ -207,7 +199,9 @@ void metric_layout(A &ar, int m, int n, int k, float **Wp, float **Dp, double **
 extern "C" size_t tg_pred_error_workspace_size(int m, int n, int k) {
   if (m < 1 || n < 1 || k < 1) return 0;
   tg::Sizer s;
-  metric_layout(s, m, n, k, nullptr, nullptr, nullptr);
+  float *Wp, *Dp;
+  double *part;
+  metric_layout(s, m, n, k, &Wp, &Dp, &part);
   return s.off + 256;
 }
 

@@ -87,15 +87,13 @@ void piv_layout(A &ar, int n, int k, PivWs *p) {
   PivWs &q = p ? *p : d;
   auto take = [&](auto *&dst, size_t cnt) {
     using T = std::remove_reference_t<decltype(*dst)>;
-    if constexpr (std::is_same_v<A, tg::Arena>) dst = ar.template take<T>(cnt);
-    else ar.template take<T>(cnt);
+    dst = ar.template take<T>(cnt);
   };
   // the two compacted H_k buffers on 2 MB boundaries (their rows are
   // gathered by the candidate steps and the fill kernel)
   auto take2m = [&](double *&dst, size_t cnt) {
     constexpr size_t AL = size_t(2) << 20;
-    if constexpr (std::is_same_v<A, tg::Arena>) dst = ar.template take_aligned<double>(cnt, AL);
-    else ar.template take_aligned<double>(cnt, AL);
+    dst = ar.template take_aligned<double>(cnt, AL);
   };
   take(q.B, size_t(k) * n);
   take(q.pp, size_t(2) * PGMAX * PPS);

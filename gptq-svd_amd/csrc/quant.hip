@@ -795,8 +795,7 @@ void quant_layout(A &ar, int m, int n, int block, QuantWs *p) {
   const int bp = (block + 31) & ~31;
   auto t = [&](auto *&dst, size_t cnt) {
     using T = std::remove_reference_t<decltype(*dst)>;
-    if constexpr (std::is_same_v<A, tg::Arena>) dst = ar.template take<T>(cnt);
-    else ar.template take<T>(cnt);
+    dst = ar.template take<T>(cnt);
   };
   QuantWs d{};
   QuantWs &q = p ? *p : d;

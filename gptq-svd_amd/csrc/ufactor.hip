@@ -780,10 +780,7 @@ static void refine_layout(Ar &ar, int k, RefineWs *w) {
   RefineWs d{};
   RefineWs &q = w ? *w : d;
   const size_t h = size_t(NU) * ((tg::cdiv(k, NU) + 1) / 2);
-  auto t = [&](double *&dst, size_t cnt) {
-    if constexpr (std::is_same_v<Ar, tg::Arena>) dst = ar.template take<double>(cnt);
-    else ar.template take<double>(cnt);
-  };
+  auto t = [&](double *&dst, size_t cnt) { dst = ar.template take<double>(cnt); };
   t(q.Ri, size_t(k) * k);
   t(q.Q, size_t(k) * k);
   t(q.G, size_t(k) * k);
@@ -796,8 +793,7 @@ static void ufac_layout(Ar &ar, int n, int k, double **A, int **info, double **W
                         RefineWs *w) {
   auto t = [&](auto *&dst, size_t cnt) {
     using T = std::remove_reference_t<decltype(*dst)>;
-    if constexpr (std::is_same_v<Ar, tg::Arena>) dst = ar.template take<T>(cnt);
-    else ar.template take<T>(cnt);
+    dst = ar.template take<T>(cnt);
   };
   double *d[3];
   int *i0;
@@ -901,8 +897,7 @@ static void urx_layout(Ar &ar, int n, int k, double **S, double **Y, double **Bm
   const size_t h = size_t(NU) * ((tg::cdiv(k, NU) + 1) / 2);
   auto t = [&](auto *&dst, size_t cnt) {
     using T = std::remove_reference_t<decltype(*dst)>;
-    if constexpr (std::is_same_v<Ar, tg::Arena>) dst = ar.template take<T>(cnt);
-    else ar.template take<T>(cnt);
+    dst = ar.template take<T>(cnt);
   };
   double *d[7];
   int *i0;
@@ -1259,8 +1254,7 @@ void hinv_layout(A &ar, int n, double **Aw, double **Yw, double **Tw, double **W
   const size_t h = size_t(NU) * ((tg::cdiv(n, NU) + 1) / 2);
   auto t = [&](auto *&dst, size_t cnt) {
     using T = std::remove_reference_t<decltype(*dst)>;
-    if constexpr (std::is_same_v<A, tg::Arena>) dst = ar.template take<T>(cnt);
-    else ar.template take<T>(cnt);
+    dst = ar.template take<T>(cnt);
   };
   double *d0, *d1, *d2, *d3, *d4;
   int *i0;

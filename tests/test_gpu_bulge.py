@@ -149,3 +149,25 @@ def test_tri_guard_fires(entry, monkeypatch):
     lib.call(entry, *args())
     torch.cuda.synchronize()
     assert all(torch.isfinite(t).all() for t in outs())
+
+
+@pytest.mark.parametrize("n", [35, 257])
+def test_workspace_exact(n):
+    """tg_band_tridiag stays inside tg_band_tridiag_workspace_size(n) bytes
+    (band storage, reflector records, progress words): with exactly that many
+    bytes passed, a poisoned tail behind them is unchanged and the result is
+    the one LAPACK gives on the band (1e-12 ||B||, as above)."""
+    from gptq_svd_amd import _lib as lib
+    A = band(n, n)
+    Ad = torch.from_numpy(A).to(DEV)
+    size, tail = lib.lib.tg_band_tridiag_workspace_size(n), 4096
+    ws = torch.full((size + tail,), 0xA5, dtype=torch.uint8, device=DEV)
+    d = torch.empty(n, dtype=torch.float64, device=DEV)
+    e = torch.empty(n, dtype=torch.float64, device=DEV)
+    lib.call("tg_band_tridiag", lib.stream(), lib.ptr(Ad), n, n, lib.ptr(d), lib.ptr(e),
+             lib.ptr(ws), size)
+    torch.cuda.synchronize()
+    assert bool((ws[size:] == 0xA5).all())
+    w = sl.eigvalsh_tridiagonal(d.cpu().numpy(), e[:n - 1].cpu().numpy())
+    ref = sl.eigvalsh(A)
+    assert np.abs(w - ref).max() <= 1e-12 * np.abs(ref).max()
