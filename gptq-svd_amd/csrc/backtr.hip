@@ -3,8 +3,10 @@
 // form for any k (q2_tfactor_kernel, q2_apply_kernel: sb_q2_tfactors,
 // sb_apply_q2, sb2st_t2_count; at the end of the file) and the few-vector
 // forms below -- and the few-vector Q1.  The level-by-level Q1 (sb_apply_q1)
-// is in band.hip, next to the forward reduction whose ytz_kernel and RowMap
-// it shares; the chase that writes the reflector records is in bulge.hip.
+// is in band.hip and, for the TSQR tree, in tsqr.hip, next to the forward
+// reduction whose ytz_kernel and RowMap it shares (the row map itself,
+// tsqr_row_fwd, is in band.h); the chase that writes the reflector records is
+// in bulge.hip.
 //
 // Z <- Q1 Q2 Z for few eigenvectors (k <= 32 columns) in ONE persistent
 // launch.
@@ -267,12 +269,6 @@ __device__ void q2_block(const BtArgs &a, __amdgpu_buffer_rsrc_t rz, int G2, int
   wave_sync();  // Vs / Ts reused by this wave's next block
 }
 
-// Stacked row s of TSQR level lv -> level-0 row (band.hip RowMap::fwd).
-__device__ inline int fwd_row(int lv, int s) {
-  for (int l = lv; l >= 1; --l) s = (s / SB_B) * SB_C + s % SB_B;
-  return s;
-}
-
 // Reflector data of one Q1 chunk for this wave: Y rows of the P = Y^T Z
 // product in MFMA A-operand order, and this thread's two entries of T.
 struct Q1Pre {
@@ -311,7 +307,7 @@ __device__ void q1_chunk(const BtArgs &a, __amdgpu_buffer_rsrc_t rz, const Q1Op 
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int rl = wid * 64 + rb * 16 + lr + 4 * q;
-      const int zr = fwd_row(d.lv, kb + min(rl, h - 1));
+      const int zr = tg::tsqr_row_fwd(d.lv, kb + min(rl, h - 1));
 #pragma unroll
       for (int cb = 0; cb < NCB; ++cb)
         F[rb][cb][q] = load_z(a, rz, int64_t(d.r0 + zr) * k + min(cb * 16 + lc, k - 1));
@@ -396,7 +392,7 @@ __device__ void q1_chunk(const BtArgs &a, __amdgpu_buffer_rsrc_t rz, const Q1Op 
     for (int q = 0; q < 4; ++q) {
       const int rl = wid * 64 + rb * 16 + lr + 4 * q;
       if (rl >= h) continue;
-      const int zr = fwd_row(d.lv, kb + rl);
+      const int zr = tg::tsqr_row_fwd(d.lv, kb + rl);
 #pragma unroll
       for (int cb = 0; cb < NCB; ++cb) {
         const int col = cb * 16 + lc;

@@ -1,8 +1,11 @@
 // The two-stage symmetric eigensolver's stages, shared constants and
 // workspace layout:
-//   band.hip    stage 1, full -> band (sy2sb, TSQR or panel-QR panels), and
-//               its level-by-level back-transformation sb_apply_q1;
+//   band.hip    stage 1, full -> band (sy2sb): the plan, the side stream, the
+//               X / M kernel and the production driver over panel-QR panels,
+//               with its back-transformation sb_apply_q1;
 //   pqr.hip     the panel QR of stage 1;
+//   sbupd.hip   the production path's W and trailing-update kernels;
+//   tsqr.hip    stage 1 and sb_apply_q1 by the TSQR tree (plans not `single`);
 //   bulge.hip   stage 2, band -> tridiagonal by bulge chasing (sb2st) with
 //               the tridiagonal guard;
 //   backtr.hip  the back-transformation Q2 (sb_apply_q2, sb_q2_tfactors) and
@@ -20,6 +23,18 @@ constexpr int SB_C = 256;   // TSQR leaf height (last leaf of a level absorbs < 
 constexpr int SB_LV = 6;    // max TSQR levels
 constexpr int PQR_NWMAX = 256;       // panel-QR workgroups (pqr.hip): 256 rows each, one per CU
 constexpr int PQR_BC_DOUBLES = 8192; // panel-QR broadcast block
+
+#define TG_CHK(x)                     \
+  do {                                \
+    hipError_t e_ = (x);              \
+    if (e_ != hipSuccess) return e_;  \
+  } while (0)
+
+// Stacked row s of TSQR level lv -> row of level 0.
+__device__ inline int tsqr_row_fwd(int lv, int s) {
+  for (int l = lv; l >= 1; --l) s = (s / SB_B) * SB_C + s % SB_B;
+  return s;
+}
 
 // One TSQR level of one panel: `rows` stacked rows split in `nc` chunks.
 struct SbLevel {
@@ -84,10 +99,9 @@ size_t sb2st_t2_count(int n);
 // control words: 4 + 4 per panel, padded to a multiple of 16 bytes
 inline size_t pq_ctl_words(int n) { return 4 + 4 * size_t(std::max(1, n / SB_B + 1)); }
 // X / M kernel: one ticket per group of 32 row blocks of 16 rows, + 1
-// X / M control words: group tickets [0, n / 256 + 7), the fused-W flag at
-// n / 256 + 7, the K-split column-block tickets from n / 256 + 8 (n / 16 + 2)
-inline size_t xm_mflag_off(int n) { return size_t(n) / 256 + 7; }
-inline size_t xm_cbt_off(int n) { return size_t(n) / 256 + 8; }
+// X / M control words: group tickets [0, n / 256 + 7), the K-split
+// column-block tickets from n / 256 + 7 (n / 16 + 2)
+inline size_t xm_cbt_off(int n) { return size_t(n) / 256 + 7; }
 inline size_t xm_tick_words(int n) { return xm_cbt_off(n) + size_t(n) / 16 + 2; }
 // K-split partial X blocks: at most 8 splits of every 32-row block
 inline size_t xm_xpart_doubles(int n) { return 8 * (size_t(n) + 32) * 32; }
@@ -136,6 +150,23 @@ void sb_layout(A &ar, int n, int kmax, const SbPlan &pl, SbBufs *bp) {
 // A (n x n symmetric, full storage, lda) -> band matrix of half-bandwidth
 // SB_B in place (full storage, zeros outside the band); reflectors in bufs.
 hipError_t sy2sb(hipStream_t st, double *A, int lda, int n, const SbPlan &pl, const SbBufs &b);
+// The same and sb_apply_q1 for plans that are not `single` (tsqr.hip).
+hipError_t sy2sb_tsqr(hipStream_t st, double *A, int lda, const SbPlan &pl, const SbBufs &b);
+hipError_t sb_apply_q1_tsqr(hipStream_t st, double *Z, int k, const SbPlan &pl, const SbBufs &b);
+// The production path's steps after a panel's X / M launch (sbupd.hip), Y, W,
+// X m x 32 with leading dimension 32:
+// W = X - Y M / 2 in place over X
+hipError_t launch_w_update(hipStream_t st, const double *Y, double *X, int m, const double *M);
+// a pair's partner: W_b = X - Ya P - Wa Q - Yb M_b / 2 in place over X, PQ as
+// the X / M launch leaves it
+hipError_t launch_w_update2(hipStream_t st, const double *Yb, double *X, int m, const double *M,
+                            const double *Ya, const double *Wa, const double *PQ);
+// the first 32 columns of A22 (the partner's panel) -= Y W^T + W Y^T
+hipError_t launch_panel_upd(hipStream_t st, double *A22, int lda, int m, const double *Y,
+                            const double *W);
+// A22 -= Y W^T + W Y^T, and with (Ya, Wa) also -= Ya Wa^T + Wa Ya^T (summed first)
+hipError_t launch_syr2k(hipStream_t st, double *A22, int lda, int m, const double *Y,
+                        const double *W, const double *Ya = nullptr, const double *Wa = nullptr);
 // Single-level plans: reads the panel-QR timeout flag (one D2H copy + sync).
 hipError_t sy2sb_timed_out(hipStream_t st, const SbPlan &pl, const SbBufs &b, bool *tmo);
 // Band (in A after sy2sb) -> tridiagonal (d, e) by bulge chasing.
@@ -154,7 +185,14 @@ hipError_t sb_apply_q2(hipStream_t st, int n, double *Z, int k, const double *V2
                        double *T2);
 // Q2 block T factors only (T2), for sb_apply_few.
 hipError_t sb_q2_tfactors(hipStream_t st, int n, const double *V2, double *T2);
-// side stream of the band reduction: fork after the work queued on st, join back into st
+// Side stream + events of the band reduction (the TSQR levels >= 1), created
+// once per device.
+struct SideStream {
+  hipStream_t s = nullptr;
+  hipEvent_t ev0[2] = {nullptr, nullptr}, ev1[2] = {nullptr, nullptr}, evj = nullptr;
+};
+hipError_t side_stream(SideStream *&out);
+// fork after the work queued on st, join back into st
 hipError_t side_fork(hipStream_t st, hipStream_t *side);
 hipError_t side_join(hipStream_t st);
 // A fork that every exit joins: join() where the side stream's work is needed

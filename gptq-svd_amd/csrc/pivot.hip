@@ -570,7 +570,7 @@ __global__ __launch_bounds__(256) void piv_panel_kernel(int n, int k, int ps, in
 // the Schur complement of the unpivoted rows is the leading (n - ps)^2 block,
 // row / column x holding the row at position ps + x (leading dimension n).
 // Each panel's Schur update writes the next compacted block into the other
-// buffer (syrk_compact_kernel), so the update touches (n - ps)^2 entries
+// buffer (syrk_compact_p_kernel), so the update touches (n - ps)^2 entries
 // instead of n^2 and a pivot's row is contiguous.
 constexpr int SEL = 1024;        // candidates
 constexpr int SEL_LDS_N = 8192;  // n up to which piv_sel_kernel stages diagonals in LDS
@@ -1562,77 +1562,14 @@ typedef double doublex4 __attribute__((ext_vector_type(4)));
 // bytes per entry of the block read and written instead of 12 with the
 // mirror; every reader takes (max, min), hk_at).  The entries are the values
 // the mirrored form wrote, bit for bit (a diagonal tile's (a, b) and (b, a)
-// are the same products summed in the same order).  The grid covers the
-// whole n x n lower triangle; tiles past the block exit.
-__global__ __launch_bounds__(256) void syrk_compact_kernel(int n, PivWs w,
-                                                           const double *__restrict__ Hc,
-                                                           double *__restrict__ Hn) {
-  __shared__ double li[PB][64], lj[PB][64];
-  __shared__ int orow[64], ocol[64];
-  const int tid = threadIdx.x;
-  const int ps2 = w.sstate[0], tn = max(w.sstate[1], 0);
-  const int nc = n - ps2;
-  const int b = blockIdx.x;
-  int I = int((sqrt(8.0 * b + 1.0) - 1.0) * 0.5);
-  while ((I + 1) * (I + 2) / 2 <= b) ++I;
-  while (I * (I + 1) / 2 > b) --I;
-  const int J = b - I * (I + 1) / 2;
-  const int i0 = 64 * I, j0 = 64 * J;
-  if (i0 >= nc) return;
-  if (tid < 64) {
-    orow[tid] = w.oidx[tn + min(i0 + tid, nc - 1)];
-  } else if (tid < 128) {
-    ocol[tid - 64] = w.oidx[tn + min(j0 + tid - 64, nc - 1)];
-  }
-  for (int e = tid; e < PB * 64; e += 256) {
-    const int l = e >> 6, c = e & 63;
-    li[l][c] = w.LT[size_t(l) * n + min(i0 + c, nc - 1)];
-    lj[l][c] = w.LT[size_t(l) * n + min(j0 + c, nc - 1)];
-  }
-  __syncthreads();
-  // rank-PB update on FP64 MFMA: waves 2 x 2 over the tile, 2 x 2 blocks of
-  // 16 x 16 each; the accumulators start from the gathered old values
-  const int lane = tid & 63, wid = tid >> 6, wm = wid >> 1, wn = wid & 1;
-  const int lr = lane & 15, lk = lane >> 4;
-  doublex4 acc[2][2];
-#pragma unroll
-  for (int ib = 0; ib < 2; ++ib)
-#pragma unroll
-    for (int jb = 0; jb < 2; ++jb)
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        acc[ib][jb][q] = Hc[hk_at(orow[wm * 32 + ib * 16 + lk + 4 * q], ocol[wn * 32 + jb * 16 + lr], n)];
-#pragma unroll
-  for (int kq = 0; kq < PB; kq += 4) {
-    double af[2], bf[2];
-#pragma unroll
-    for (int ib = 0; ib < 2; ++ib) af[ib] = -li[kq + lk][wm * 32 + ib * 16 + lr];
-#pragma unroll
-    for (int jb = 0; jb < 2; ++jb) bf[jb] = lj[kq + lk][wn * 32 + jb * 16 + lr];
-#pragma unroll
-    for (int ib = 0; ib < 2; ++ib)
-#pragma unroll
-      for (int jb = 0; jb < 2; ++jb)
-        acc[ib][jb] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[ib], bf[jb], acc[ib][jb], 0, 0, 0);
-  }
-#pragma unroll
-  for (int ib = 0; ib < 2; ++ib)
-#pragma unroll
-    for (int jb = 0; jb < 2; ++jb)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int rl = wm * 32 + ib * 16 + lk + 4 * q, cl = wn * 32 + jb * 16 + lr;
-        const int gi = i0 + rl, gj = j0 + cl;
-        if (gi < nc && gj < nc && gi >= gj) Hn[size_t(gi) * n + gj] = acc[ib][jb][q];
-      }
-}
-
-// Persistent form of syrk_compact_kernel (the default): two workgroups per
-// CU loop over the tiles of the leading (n - ps2)^2 block (its size read on
-// the device); the next tile's gathered old values are loaded while this
-// tile is multiplied and written (its row / column indices one step earlier
-// still), so the memory pipe does not idle through each workgroup's MFMA,
-// epilogue and dispatch.  Same arithmetic per entry as syrk_compact_kernel.
+// are the same products summed in the same order).  Rank-PB update on FP64
+// MFMA: waves 2 x 2 over the tile, 2 x 2 blocks of 16 x 16 each, the
+// accumulators starting from the gathered old values.
+// Persistent: two workgroups per CU loop over the tiles of the leading
+// (n - ps2)^2 block (its size read on the device); the next tile's gathered
+// old values are loaded while this tile is multiplied and written (its row /
+// column indices one step earlier still), so the memory pipe does not idle
+// through each workgroup's MFMA, epilogue and dispatch.
 __global__ __launch_bounds__(256, 2) void syrk_compact_p_kernel(int n, PivWs w,
                                                                 const double *__restrict__ Hc,
                                                                 double *__restrict__ Hn) {
@@ -1812,9 +1749,6 @@ static int pivot_core_sel(hipStream_t st, PivWs &w, int n, int k) {
   if (lds > 48 * 1024)
     TG_HIP(hipFuncSetAttribute((const void *)piv_sel_kernel,
                                hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
-  // TG_SYR2K_PERSIST=0: one tile per workgroup (development switch, per call)
-  const char *ps = getenv("TG_SYR2K_PERSIST");
-  const bool persist = !(ps && ps[0] == '0');
   const tg::XcdInfo xi = tg::xcd_info();
   const int ncu = std::max(1, xi.xcds * xi.cus_per_xcd);
   // compacted Schur complements alternate between the two buffers
@@ -1822,12 +1756,8 @@ static int pivot_core_sel(hipStream_t st, PivWs &w, int n, int k) {
   double *hn = w.Hk2;
   auto schur_compact = [&](int rows) -> hipError_t {
     const int nt = tg::cdiv(rows, 64);
-    if (persist)
-      hipLaunchKernelGGL(syrk_compact_p_kernel, dim3(std::min(nt * (nt + 1) / 2, 2 * ncu)),
-                         dim3(256), 0, st, n, w, hc, hn);
-    else
-      hipLaunchKernelGGL(syrk_compact_kernel, dim3(nt * (nt + 1) / 2), dim3(256), 0, st, n, w, hc,
-                         hn);
+    hipLaunchKernelGGL(syrk_compact_p_kernel, dim3(std::min(nt * (nt + 1) / 2, 2 * ncu)),
+                       dim3(256), 0, st, n, w, hc, hn);
     const hipError_t e = hipGetLastError();
     double *t = const_cast<double *>(hc);
     hc = hn;

@@ -109,7 +109,8 @@ def test_orthogonality_n4096(kind, first, count):
 
 def test_panel_pairs_large_n(monkeypatch):
     """n = 9000: the default band reduction pairs the panels with >= 6144
-    trailing rows (merged rank-128 updates, corrections on a side stream);
+    trailing rows (merged rank-128 updates, the corrections' products formed
+    in the partner's X / M launch);
     its eigenvalues match the unpaired reduction's (TG_SB_PAIR=0) to
     1e-12 ||H|| and repeat bit for bit."""
     from gptq_svd_amd import _lib as lib
@@ -326,30 +327,37 @@ def test_invit_factor_once_bit_identical(n, count, kind, iters, monkeypatch):
     assert np.array_equal(vectors("0"), ref)
 
 
-@pytest.mark.parametrize("n", [4096, 2000, 7000])
-def test_xm_fused_w_bit_identical(n, monkeypatch):
-    """W = X - Y M / 2 formed inside the X / M launch (csrc/band.hip
-    xm_fused_w, TG_XM_FUSE_W=1: every workgroup waits for the last arriver's
-    M, then updates its own rows; measured no faster, so opt-in) gives the
-    reduced band of w_update_kernel (the default) bit for bit: the same fma
-    chain per entry, so the eigenvalues agree exactly.  n = 2000: a ragged last row block; n = 7000: panels of both
-    X / M forms (16 and 32 columns per workgroup) and panel pairs."""
+@pytest.mark.parametrize("n", [577, 1025, 1999])
+def test_panel_pairs_small_n(n, monkeypatch):
+    """TG_SB_PAIR=1 pairs every panel whose partner has >= 256 rows, and a
+    partner's X / M launch is always xm_kernel<2> with the pair products
+    (csrc/band.hip launch_xm), here on partners of 256 to ~2000 rows: odd
+    widths on every panel, a ragged last block, one group of workgroups
+    (n = 577, 1025) and two (n = 1999), the default K split active.
+    Eigenvalues vs LAPACK and vs the unpaired reduction (TG_SB_PAIR=0) to
+    1e-12 max|lambda| (the bound of test_xm_packed_odd_width and
+    test_xm_ksplit at these sizes), and a second paired run bit for bit."""
     from gptq_svd_amd import _lib as lib
-    H = torch.from_numpy(_wishart(n, 41)).to(DEV)
+    H = _wishart(n, 61)
     ws = lib.workspace(lib.lib.tg_eigh_workspace_size(n), torch.device(DEV))
 
-    def values(flag):
-        monkeypatch.setenv("TG_XM_FUSE_W", flag)
-        A = H.clone()
+    def values(pair):
+        monkeypatch.setenv("TG_SB_PAIR", pair)
+        A = torch.from_numpy(H).to(DEV)
         w = torch.empty(n, dtype=torch.float64, device=DEV)
         lib.call("tg_eigh_values", lib.stream(), lib.ptr(A), n, n, lib.ptr(w), lib.ptr(ws),
                  ws.numel())
         torch.cuda.synchronize()
-        return w.cpu().numpy()
+        return np.sort(w.cpu().numpy())
 
-    ref = values("0")
-    for _ in range(2):
-        assert np.array_equal(values("1"), ref)
+    paired, plain = values("1"), values("0")
+    ref = np.linalg.eigvalsh(H)
+    nrm = np.abs(ref).max()
+    print(f"n={n}: paired vs LAPACK {np.abs(paired - ref).max() / nrm:.2e}, "
+          f"vs unpaired {np.abs(paired - plain).max() / nrm:.2e} max|lambda|")
+    assert np.abs(paired - ref).max() <= 1e-12 * nrm
+    assert np.abs(paired - plain).max() <= 1e-12 * nrm
+    assert np.array_equal(values("1"), paired)
 
 
 @pytest.mark.parametrize("n,count", [(4096, 14), (3001, 5)])

@@ -54,13 +54,9 @@ def rel(a, b):
     {"TG_SB_PAIR": "1"},
     {"TG_SB_PAIR": "0"},
     {"TG_SB_PAIR": "1", "TG_XM_NBC": "2"},
-    {"TG_SB_PAIR": "1", "TG_XM_NBC": "2", "TG_SB_PAIR_SIDE": "1"},
-    {"TG_SYR2K_PERSIST": "0"},
-    {"TG_SYR2K_PERSIST": "0", "TG_SB_PAIR": "1"},
     {"TG_XM_ASM": "0"},
     {"TG_XM_ASM": "0", "TG_XM_NBC": "2"},
     {"TG_XM_NBC": "2"},
-    {"TG_XM_FUSE_W": "1"},
     {"TG_XM_KSPLIT": "1"},
     {"TG_XM_KSPLIT": "3"},
     {"TG_URX_SMALLM": "1"},

@@ -4,6 +4,8 @@ by default, ROWS x n fp16 rows, default 3n/4), REPS timed solves; prints the
 median / min and a hash of (perm, R_x, U) so builds that must be bit-identical
 can be compared (and a second one of the spectrum S).  BAND=35,257,...: first
 hash (d, e, V2) of tg_band_tridiag on a seeded band of those widths.
+EIGH=2048,...: hash of the reduced band tg_eigh_values leaves in A and of its
+eigenvalues (what (d, e) determine) on a seeded symmetric matrix.
     N=12288 python tools/lib_ab.py gptq-svd_amd/variants/lib_band_v*.so"""
 import os
 import subprocess
@@ -32,7 +34,19 @@ for n in [int(x) for x in os.environ.get("BAND", "").split(",") if x]:
     for t in (d, e[:n - 1], ws[off: off + max(1, n - 2) * smax * 32 * 8]):
         h.update(t.contiguous().cpu().numpy().tobytes())
     print(f"{name} band n={n}: hash (d, e, V2) {h.hexdigest()[:16]}", flush=True)
-for n in [int(x) for x in os.environ.get("N", "4096,12288").split(",")]:
+for n in [int(x) for x in os.environ.get("EIGH", "").split(",") if x]:
+    torch.manual_seed(n)
+    X = torch.randn(3 * n // 2, n, dtype=torch.float64, device=dev)
+    A = (X.T @ X / X.shape[0]).contiguous()
+    del X
+    ws = _lib.workspace(_lib.lib.tg_eigh_workspace_size(n), dev)
+    w = torch.empty(n, dtype=torch.float64, device=dev)
+    _lib.call("tg_eigh_values", _lib.stream(), _lib.ptr(A), n, n, _lib.ptr(w), _lib.ptr(ws), ws.numel())
+    torch.cuda.synchronize()
+    ha, hw = (hashlib.sha1(t.cpu().numpy().tobytes()).hexdigest()[:16] for t in (A, w))
+    print(f"{name} eigh n={n}: hash band {ha}, eigenvalues {hw}", flush=True)
+    del A, ws
+for n in [int(x) for x in os.environ.get("N", "4096,12288").split(",") if x]:
     rows = int(float(os.environ.get("ROWS", "0.75")) * n)
     torch.manual_seed(1)
     acc = g.HessianAccumulator(n, dev)
