@@ -107,6 +107,9 @@ _SIGS = {
                       _i64], _i),
     "tg_hadamard": ([_vp, _vp, _i, _i64, _i, _i64, _i, _vp, _i, _vp, _i, _i64], _i),
     "tg_hadamard_sym": ([_vp, _vp, _i, _i64, _i, _vp], _i),
+    "tg_qgemm_grouped_workspace_size": ([_i, _i, _i, _i], _sz),
+    "tg_qgemm_grouped": ([_vp, _vp, _i, _i, _i64, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i,
+                          _i, _i, _vp, _vp, _i, _i64, _vp, _sz], _i),
 }
 
 EXPORTED = []

@@ -39,6 +39,17 @@ Hadamard rotation (``quantize_model(rotate=...)``): a rotated linear also has
   layer's input.  Checkpoints without the key are read exactly
   as before.
 
+Mixture of Experts (A19): an experts module (3-D ``gate_up_proj`` (E, 2I, H) and
+``down_proj`` (E, H, I)) is packed as two stacks.  `packed` holds them under the
+parameters' names, ``<experts>.gate_up_proj`` and ``<experts>.down_proj``, each
+with 3-D ``qweight`` (E, in*b/32, out), ``qzeros`` (E, G, out*b/32) and ``scales``
+(E, G, out) (MXFP4: ``qweight`` and uint8 ``scales`` (E, in/32, out)); expert e's
+slice is exactly the 2-D image above.  They are written as
+``<experts>.gate_up_qweight`` ... ``<experts>.down_scales`` (the buffers of
+``qlinear.QuantExperts``; no ``g_idx``) in place of the two parameters, and
+``quantize_config.json`` lists the module names under ``"experts"``.  Checkpoints
+without the key are read exactly as before.
+
 ``load_quantized`` is the way back: it puts the packed tensors into
 ``qlinear.QuantLinear`` (``qlinear.MXQuantLinear`` for MXFP4) modules of a
 model, which run them without unpacking.
@@ -76,7 +87,24 @@ def save_quantized(path: str, model: torch.nn.Module, packed: Dict[str, Dict[str
     tensors: Dict[str, torch.Tensor] = {}
     lowrank = 0
     blocks: Dict[str, int] = {}
+    experts = set()
     for name, t in packed.items():
+        if t["qweight"].dim() == 3:              # a stack of an experts module
+            mod, _, leaf = name.rpartition(".")
+            if leaf not in ("gate_up_proj", "down_proj"):
+                raise ValueError(f"{name}: a stacked entry must be named gate_up_proj or down_proj")
+            if f"{mod}.gate_up_proj" not in packed or f"{mod}.down_proj" not in packed:
+                raise ValueError(f"{mod}: gate_up_proj and down_proj come together")
+            if mx and t["scales"].dtype != torch.uint8:
+                raise ValueError(f"{name}: MXFP4 scales must be uint8, got {t['scales'].dtype}")
+            stem = f"{mod}.{leaf[:-len('_proj')]}"
+            tensors[f"{stem}_qweight"] = t["qweight"].contiguous().cpu()
+            tensors[f"{stem}_scales"] = (t["scales"] if mx else t["scales"].to(scale_dtype)) \
+                .contiguous().cpu()
+            if not mx:
+                tensors[f"{stem}_qzeros"] = t["qzeros"].contiguous().cpu()
+            experts.add(mod)
+            continue
         if (t.get("had_sign") is None) != (not t.get("had_block")):
             raise ValueError(f"{name}: had_sign and had_block come together")
         if t.get("had_sign") is not None:
@@ -104,7 +132,7 @@ def save_quantized(path: str, model: torch.nn.Module, packed: Dict[str, Dict[str
         tensors[f"{name}.g_idx"] = (torch.arange(in_features, dtype=torch.int32) // g)
     for k, v in sd.items():
         mod = k.rsplit(".", 1)[0]
-        if mod in packed and k.endswith(".weight"):
+        if (mod in packed and k.endswith(".weight")) or (mod in experts and k in packed):
             continue  # replaced by the packed tensors
         tensors[k] = v.detach().contiguous().cpu()
     # tied parameters share storage: safetensors refuses aliases, so clone
@@ -126,6 +154,8 @@ def save_quantized(path: str, model: torch.nn.Module, packed: Dict[str, Dict[str
         qc["lowrank"] = lowrank
     if blocks:
         qc["rotation"] = {"kind": "hadamard", "blocks": blocks}
+    if experts:
+        qc["experts"] = sorted(experts)
     if extra_config:
         qc["truncgptq"] = extra_config
     with open(os.path.join(path, "quantize_config.json"), "w") as f:
@@ -180,6 +210,50 @@ def _rotation_of(tensors: Dict[str, torch.Tensor], name: str, blocks: Dict[str, 
     return (blocks[name], tensors[keys["had_sign"]]) if name in blocks else None
 
 
+def _load_experts(model: torch.nn.Module, tensors: Dict[str, torch.Tensor], qc: Dict[str, Any],
+                  used: set) -> None:
+    """Every module listed under ``"experts"`` becomes a ``qlinear.QuantExperts``
+    holding its two packed stacks; `used` gains the tensors taken."""
+    from .qlinear import QuantExperts
+    mx = qc.get("checkpoint_format") == "mxfp4"
+    for name in qc.get("experts", []):
+        try:
+            mod = model.get_submodule(name)
+        except AttributeError:
+            raise KeyError(f"{name}: packed in the checkpoint but absent from the model") from None
+        if not _is_experts(mod):
+            raise TypeError(f"{name}: expected an experts module with 3-D gate_up_proj and "
+                            f"down_proj, found {type(mod).__name__}")
+        stacks = []
+        for stem in ("gate_up", "down"):
+            keys = {k: f"{name}.{stem}_{k}" for k in (("qweight", "scales") if mx else
+                                                      ("qweight", "qzeros", "scales"))}
+            for k in keys.values():
+                if k not in tensors:
+                    raise KeyError(f"{k} is missing from the checkpoint")
+            stacks.append({k: tensors[v] for k, v in keys.items()})
+            used.update(keys.values())
+        try:
+            q = QuantExperts.from_packed(stacks[0], stacks[1], int(qc["bits"]),
+                                         int(qc["group_size"]), "mxfp4" if mx else "int",
+                                         act_fn=getattr(mod, "act_fn", None),
+                                         device=mod.gate_up_proj.device)
+        except ValueError as e:
+            raise ValueError(f"{name}: {e}") from None
+        if (q.num_experts, 2 * q.intermediate_dim, q.hidden_dim) != tuple(mod.gate_up_proj.shape):
+            raise ValueError(f"{name}: packed stacks are for gate_up_proj "
+                             f"{(q.num_experts, 2 * q.intermediate_dim, q.hidden_dim)}, the "
+                             f"model's is {tuple(mod.gate_up_proj.shape)}")
+        _set_submodule(model, name, q)
+
+
+def _is_experts(mod: torch.nn.Module) -> bool:
+    """An experts module by duck type: 3-D parameters gate_up_proj and down_proj."""
+    gu, dn = getattr(mod, "gate_up_proj", None), getattr(mod, "down_proj", None)
+    return isinstance(gu, torch.Tensor) and isinstance(dn, torch.Tensor) \
+        and gu.dim() == 3 and dn.dim() == 3
+
+
 def _set_submodule(model: torch.nn.Module, name: str, new: torch.nn.Module) -> None:
     parent_name, _, leaf = name.rpartition(".")
     parent = model.get_submodule(parent_name) if parent_name else model
@@ -194,7 +268,8 @@ def load_quantized(model: torch.nn.Module, path: str, device=None,
     holding the packed tensors (bias kept, in the linear's dtype); every other
     tensor is loaded as is.  A linear with ``<name>.lr_a`` / ``<name>.lr_b`` gets
     them as its low-rank correction, and one listed in the ``"rotation"`` entry its
-    ``had_sign`` and block (the module then rotates its input).
+    ``had_sign`` and block (the module then rotates its input).  Every module listed
+    under ``"experts"`` becomes a ``qlinear.QuantExperts`` with the two packed stacks.
     ``quantize_config.json`` must be a static-group
     ``desc_act=false`` configuration with supported bits, and every ``g_idx``
     must be the trivial ``arange(in) // group`` map (act-order checkpoints are
@@ -212,6 +287,9 @@ def load_quantized(model: torch.nn.Module, path: str, device=None,
             raise ValueError(f"act_format={act_format!r} needs an mxfp4 checkpoint; this one is "
                              f"{fmt!r}")
     tensors, qc = read_quantized(path)
+    if act_format is not None and qc.get("experts"):
+        raise ValueError("act_format cannot be combined with a Mixture-of-Experts checkpoint "
+                         "(the grouped kernel takes 16-bit activations)")
     bits, group = int(qc["bits"]), int(qc["group_size"])
     blocks = _rotation_blocks(qc, tensors)
     if qc.get("checkpoint_format") == "mxfp4":
@@ -229,6 +307,7 @@ def load_quantized(model: torch.nn.Module, path: str, device=None,
                          "zero points) and mxfp4 are supported")
     names = [k[:-len(".qweight")] for k in tensors if k.endswith(".qweight")]
     used = set()
+    _load_experts(model, tensors, qc, used)
     for name in names:
         try:
             lin = model.get_submodule(name)
@@ -274,6 +353,7 @@ def _load_mx(model: torch.nn.Module, tensors: Dict[str, torch.Tensor], qc: Dict[
         raise ValueError("quantize_config.json: desc_act=true (act-order) checkpoints are not "
                          "supported")
     used = set()
+    _load_experts(model, tensors, qc, used)
     for name in [k[:-len(".qweight")] for k in tensors if k.endswith(".qweight")]:
         try:
             lin = model.get_submodule(name)

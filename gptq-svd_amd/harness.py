@@ -100,6 +100,42 @@ def get_sequenced_groups(layer: nn.Module) -> List[List[str]]:
     return groups
 
 
+def experts_of(layer: nn.Module):
+    """(name, module) of the decoder layer's experts module -- by duck type, a
+    submodule with 3-D parameters ``gate_up_proj`` (E, 2I, H) and ``down_proj``
+    (E, H, I), as ``Qwen3MoeExperts`` / ``MixtralExperts`` keep them -- or None."""
+    from .export import _is_experts
+    for name, mod in layer.named_modules():
+        if _is_experts(mod):
+            return name, mod
+    return None
+
+
+def _check_experts(model: nn.Module, world: int, **on) -> None:
+    """ValueError when the model has an experts module and the run asks for what
+    the experts path does not do (`on`: option name -> truthy when asked for), or
+    a layer puts dense MLP linears or shared experts beside its experts module."""
+    try:
+        layers = get_layers(model)
+    except ValueError:          # no decoder layers: nothing to refuse; the run reports it
+        return
+    for i, layer in enumerate(layers):
+        if experts_of(layer) is None:
+            continue
+        for opt, val in on.items():
+            if val:
+                raise ValueError(f"{opt} cannot be combined with a Mixture-of-Experts model "
+                                 f"(layer {i} has an experts module)")
+        if world > 1:
+            raise ValueError("Mixture-of-Experts models are single-process")
+        dense = [n for g in get_sequenced_groups(layer) for n in g
+                 if n.startswith("mlp.") or n in ("fc1", "fc2")]
+        dense += [n for n, _ in layer.named_modules() if "shared_expert" in n]
+        if dense:
+            raise ValueError(f"layer {i} has dense MLP linears or shared experts beside its "
+                             f"experts module ({dense[0]}); they are not supported")
+
+
 def adaptive_eps(layer_name: str, base_eps: float) -> float:
     """quantize.py:17-20: down_proj / o_proj use a 10x smaller eps."""
     if any(x in layer_name for x in ["down_proj", "o_proj"]):
@@ -426,6 +462,23 @@ def quantize_model(model: nn.Module, input_ids_list: Sequence[torch.Tensor], mod
     ``layer_stats`` entry gains ``rotate_block``.  Works in all three modes, with
     both weight formats, `clip_search` and `lowrank`; single process only
     (ValueError before any work in the multi-GPU mode).
+    Mixture of Experts (A19): a decoder layer that owns an experts module (a
+    submodule with 3-D parameters ``gate_up_proj`` (E, 2I, H) and ``down_proj``
+    (E, H, I); ``experts_of``) gets two more sequenced groups after the attention
+    groups.  One forward pre-hook on the module reads ``(hidden_states,
+    top_k_index)`` and feeds every expert's routed rows to that expert's own
+    accumulator; the E slices of ``gate_up_proj`` are then solved one after
+    another with the run's `mode` and written back.  The layer runs again and the
+    same hook accumulates ``act_fn(gate) * up`` of each routed block, formed from
+    the written-back weights, for ``down_proj``.  An expert that received no
+    calibration row is solved with H = I (round-to-nearest on its grid) and
+    counted in the stack's ``layer_stats`` entry as ``experts_without_rows``;
+    ``rank`` is there the list of the experts' ranks.  The router stays as it is.
+    With ``pack=True``, ``packed`` gains ``<experts>.gate_up_proj`` and
+    ``<experts>.down_proj`` with 3-D ``qweight`` / ``qzeros`` / ``scales``
+    (``export.save_quantized``).  `lowrank`, `rotate`, `clip_search`, the multi-GPU
+    mode, and layers with dense MLP linears or shared experts beside the experts
+    module raise ValueError before any work.
     `offload`: move each layer to `device` for its turn and back to the CPU
     afterwards (the reference's policy, quantize.py:101, :239); by default
     the model stays where it is (a whole 8B/70B model fits in 288 GB).
@@ -477,6 +530,7 @@ def quantize_model(model: nn.Module, input_ids_list: Sequence[torch.Tensor], mod
         if _world(pg)[0] > 1:
             raise ValueError("rotate is single-process")
         _check_rotate(model, rotate)
+    _check_experts(model, _world(pg)[0], lowrank=lowrank, rotate=rotate, clip_search=clip_search)
     # passed on only when the rotation is on, so a run without it is unchanged
     rot_kw = dict(rotate=rotate, rotate_seed=int(rotate_seed)) if rotate else {}
     # passed on only when the correction is on, so a run without it is unchanged
@@ -673,6 +727,99 @@ def quantize_model(model: nn.Module, input_ids_list: Sequence[torch.Tensor], mod
         if clock:
             clock.stop("quantize", ev)
 
+    def solve_experts(i, ex, ename, pname, accs):
+        """Quantise the E slices of the experts module's parameter `pname`, one
+        after another, each against its own accumulator (a batched small-n solve
+        is a later step).  An expert that no calibration row
+        reached is solved with H = I: U = I, no error to propagate, i.e.
+        round-to-nearest on its grid."""
+        param = getattr(ex, pname)
+        E, _, n_in = param.shape
+        cur_eps = adaptive_eps(pname, eps) if use_adaptive_eps else eps
+        t0 = time.time()
+        ev = clock.start() if clock else None
+        ranks, without, parts = [], 0, []
+        for e in range(E):
+            acc = accs[e]
+            R_x = None
+            if acc.n_samples == 0:
+                without += 1
+                R = torch.eye(n_in, dtype=torch.float64, device=param.device)
+                perm = torch.arange(n_in, device=param.device)
+            elif mode == "svd":
+                R, perm = process_sketch(acc.get_scaled_sketch(), threshold=cur_eps,
+                                         threshold_method=threshold_method)
+            elif mode == "eigh":
+                R, R_x, perm = process_hessian_alt(acc.get_hessian(), threshold=cur_eps,
+                                                   threshold_method=threshold_method)
+            else:
+                R, perm = process_hessian(acc.get_hessian(), actorder=actorder,
+                                          damp_percent=damp_percent)
+            accs[e] = None
+            q = Quantizer(w_bits=w_bits, group_size=group_size, sym=sym, **fmt_kw)
+            Wq, k = gptq_fwrd(param.data[e].float(), R, q, perm, block_size=block_size,
+                              use_triton=(mode != "gptq"), R_x=R_x)
+            param.data[e].copy_(Wq)
+            ranks.append(k if mode != "gptq" else "N/A")
+            if pack:
+                parts.append(pack_quantized(q))
+        if pack:
+            qw, qz, sc = zip(*parts)
+            packed[f"{qual.get(id(ex), f'layer_{i}.{ename}')}.{pname}"] = dict(
+                qweight=torch.stack(qw), qzeros=None if qz[0] is None else torch.stack(qz),
+                scales=torch.stack(sc))
+        if clock:
+            clock.stop("quantize", ev)
+        dt = time.time() - t0
+        logging.info(f"   {pname: <15} | {E} experts, {without} without rows | Time: {dt:.2f}s")
+        entry = {"name": f"layer_{i}.{ename}.{pname}", "rank": ranks, "time": dt, "experts": E,
+                 "experts_without_rows": without}
+        if fmt_kw:
+            entry["weight_format"] = weight_format
+        stats.append(entry)
+
+    def experts_groups(i, layer, ename, ex, gi):
+        """The two sequenced groups of an experts module, after the attention
+        groups: gate_up_proj on each expert's routed rows, then -- the layer run
+        again with the quantised gate_up -- down_proj on act_fn(gate) * up of the
+        same rows, formed from the written-back weights as the module's own
+        forward forms them."""
+        E, _, H = ex.gate_up_proj.shape
+        for pname, n_in in (("gate_up_proj", H), ("down_proj", ex.down_proj.shape[2])):
+            logging.info(f"[Layer {i + 1}/{len(layers)}] Group {gi + 1}: {ename}.{pname}")
+            if mode == "svd":
+                shim = type("In", (), {"in_features": n_in})
+                accs = [Sketcher(shim, int(n_in * sketch_ratio), device=device, seed=sketch_seed)
+                        for _ in range(E)]
+            else:
+                accs = [HessianAccumulator(n_in, device=device) for _ in range(E)]
+
+            def hook(mod, args, kwargs, pname=pname, accs=accs):
+                hs = args[0] if args else kwargs["hidden_states"]
+                idx = args[1] if len(args) > 1 else kwargs["top_k_index"]
+                hs = hs.reshape(-1, hs.shape[-1])
+                for e in range(E):
+                    x = hs[(idx == e).any(dim=-1)]
+                    if x.shape[0] == 0:
+                        continue
+                    if pname == "down_proj":
+                        gate, up = nn.functional.linear(x, mod.gate_up_proj[e]).chunk(2, dim=-1)
+                        x = mod.act_fn(gate) * up
+                    add(accs[e], x)
+                if early_stop:
+                    raise _Stop
+
+            h = ex.register_forward_pre_hook(hook, with_kwargs=True)
+            ev = clock.start() if clock else None
+            try:
+                run_layer(layer, None)
+            finally:
+                h.remove()
+            if clock:
+                clock.stop("calib_forward", ev)
+            solve_experts(i, ex, ename, pname, accs)
+            gi += 1
+
     def batches():
         for j in range(0, n_samples, batch_size):
             x = inps[j: j + batch_size]
@@ -701,6 +848,9 @@ def quantize_model(model: nn.Module, input_ids_list: Sequence[torch.Tensor], mod
                 clock.stop("calib_forward", ev)
             solve_group(i, layer, names, acc, gi)
             del acc
+        ex = experts_of(layer)
+        if ex is not None:
+            experts_groups(i, layer, ex[0], ex[1], len(get_sequenced_groups(layer)))
         ev = clock.start() if clock else None
         run_layer(layer, outs)
         if clock:

@@ -36,6 +36,13 @@ words of sign bits) and ``rotate_block``.  Its forward first computes
 ``x' = x Q`` in the activation dtype (``hadamard``, one ``tg_hadamard`` launch)
 and feeds x' to everything that took x: ``y = x' W'^^T (+ (x' lr_b^T) lr_a^T)
 + bias``.
+
+Mixture of Experts (A19): ``QuantExperts`` replaces a layer's experts module
+(3-D ``gate_up_proj`` (E, 2I, H) and ``down_proj`` (E, H, I), the layout of
+``Qwen3MoeExperts`` / ``MixtralExperts``) and keeps both stacks packed, in either
+weight format.  Its forward sorts the token-expert assignments by expert on the
+device and runs two ``tg_qgemm_grouped`` calls (``qgemm_grouped``), with no host
+synchronisation and no atomics.
 """
 from __future__ import annotations
 
@@ -48,7 +55,8 @@ from ._lib import (ACT_FORMATS, DTYPES, TG_FMT_MXFP4, call, lib, ptr, require_cu
                    workspace)
 
 __all__ = ["QuantLinear", "dequantize_packed", "MXQuantLinear", "dequantize_packed_mx",
-           "quantize_act_mx", "dequantize_act_mx", "add_lowrank", "hadamard"]
+           "quantize_act_mx", "dequantize_act_mx", "add_lowrank", "hadamard", "QuantExperts",
+           "qgemm_grouped"]
 
 _BITS = (2, 3, 4, 8)
 
@@ -617,3 +625,177 @@ class MXQuantLinear(nn.Module):
                 if lr:
                     _lowrank_finish(x2, T, ldx, out, self.lr_a, self.lr_b, bias, y)
         return y.reshape(*x.shape[:-1], m)
+
+
+# ---------------------------------------------------------------------------
+# Mixture of Experts (A19)
+# ---------------------------------------------------------------------------
+def qgemm_grouped(x: torch.Tensor, rows: Optional[torch.Tensor], offsets: torch.Tensor,
+                  qweight: torch.Tensor, qzeros: Optional[torch.Tensor], scales: torch.Tensor,
+                  w_bits: int, group_size: int, row_scale: Optional[torch.Tensor] = None,
+                  dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """``Y[i] = row_scale[i] * x[rows[i]] @ W^_e^T`` for every slot i of expert e,
+    ``offsets[e] <= i < offsets[e + 1]`` (``tg_qgemm_grouped``).  x (T, n) fp16 /
+    bf16; rows int32 (R,) or None (slot i reads row i); offsets int32 (E + 1,);
+    qweight (E, n*b/32, m) with qzeros (E, G, m*b/32) and scales (E, G, m), or
+    ``qzeros=None`` with uint8 scales (E, n/32, m) for MXFP4; row_scale fp32 (R,)
+    or None.  Returns (R, m) of `dtype` (x's, or float32).  Everything stays on
+    the device: nothing is read back."""
+    require_cuda(x, "qgemm_grouped input")
+    if x.dtype not in (torch.float16, torch.bfloat16):
+        raise RuntimeError(f"qgemm_grouped takes float16 or bfloat16 activations, got {x.dtype} "
+                           "(there is no fp32 kernel and no fallback)")
+    E, nw, m = qweight.shape
+    mx = qzeros is None
+    n = nw * 32 // w_bits
+    T = x.shape[0]
+    R = T if rows is None else rows.numel()
+    dtype = x.dtype if dtype is None else dtype
+    if x.dim() != 2 or x.shape[1] != n:
+        raise ValueError(f"qgemm_grouped: x must be (T, {n}) for this qweight, got {tuple(x.shape)}")
+    for what, t, dt, numel in (("rows", rows, torch.int32, R), ("offsets", offsets, torch.int32, E + 1),
+                               ("row_scale", row_scale, torch.float32, R)):
+        if t is not None and (t.dtype != dt or t.device != x.device or t.numel() != numel
+                              or not t.is_contiguous()):
+            raise ValueError(f"qgemm_grouped: {what} must be a contiguous {dt} tensor of {numel} "
+                             f"elements on {x.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    y = torch.empty((R, m), dtype=dtype, device=x.device)
+    if R == 0:
+        return y
+    if x.stride(1) != 1 or (T > 1 and x.stride(0) < n):
+        x = x.contiguous()
+    ldx = x.stride(0) if T > 1 else n
+    with torch.cuda.device(x.device):
+        nbytes = lib.tg_qgemm_grouped_workspace_size(R, E, m, n)
+        ws = workspace(nbytes, x.device)
+        call("tg_qgemm_grouped", stream(), ptr(x), DTYPES[x.dtype], T, ldx, ptr(rows), ptr(offsets),
+             R, E, ptr(qweight), ptr(qzeros), ptr(scales), 0 if mx else DTYPES[scales.dtype],
+             TG_FMT_MXFP4 if mx else 0, m, n, 32 if mx else group_size, w_bits, ptr(row_scale),
+             ptr(y), DTYPES[dtype], m, ptr(ws), nbytes)
+    return y
+
+
+class QuantExperts(nn.Module):
+    """A layer's experts with both weight stacks packed: the drop-in for a module
+    with ``gate_up_proj`` (E, 2I, H), ``down_proj`` (E, H, I) and
+    ``forward(hidden_states, top_k_index, top_k_weights)``.  Buffers (the
+    checkpoint's keys): ``gate_up_qweight`` (E, H*b/32, 2I), ``gate_up_qzeros``
+    (E, G, 2I*b/32), ``gate_up_scales`` (E, G, 2I) and the same three for ``down``
+    with H and I exchanged; every ``[e]`` is what ``pack_quantized`` returns for
+    that expert.  ``weight_format="mxfp4"``: no ``qzeros``, uint8 ``scales``
+    (E, in/32, out), bits 4 and group 32.  There is no bias."""
+
+    def __init__(self, num_experts: int, hidden_dim: int, intermediate_dim: int, w_bits: int = 4,
+                 group_size: int = -1, weight_format: str = "int",
+                 scale_dtype: torch.dtype = torch.float16, act_fn=None, device=None):
+        super().__init__()
+        if weight_format not in ("int", "mxfp4"):
+            raise ValueError(f"weight_format must be 'int' or 'mxfp4', got {weight_format!r}")
+        mx = weight_format == "mxfp4"
+        if mx:
+            w_bits, group_size = 4, 32
+        if w_bits not in _BITS:
+            raise ValueError(f"w_bits must be one of {_BITS}, got {w_bits}")
+        E, H, I = int(num_experts), int(hidden_dim), int(intermediate_dim)
+        if not 1 <= E <= 256:
+            raise ValueError(f"QuantExperts takes 1 to 256 experts, got {E}")
+        for n_in, n_out in ((H, 2 * I), (I, H)):
+            g = group_size if group_size > 0 else n_in
+            if n_in % 32 or g % 32 or n_in % g or (n_out * w_bits) % 32:
+                raise ValueError(
+                    f"QuantExperts needs in % 32 == 0, group % 32 == 0 dividing in and out * bits "
+                    f"% 32 == 0 for both stacks (got hidden={H}, intermediate={I}, "
+                    f"group={group_size}, bits={w_bits})")
+        self.num_experts, self.hidden_dim, self.intermediate_dim = E, H, I
+        self.w_bits, self.group_size, self.weight_format = int(w_bits), int(group_size), weight_format
+        self.act_fn = act_fn if act_fn is not None else nn.functional.silu
+        for name, n_in, n_out in (("gate_up", H, 2 * I), ("down", I, H)):
+            G = n_in // (group_size if group_size > 0 else n_in)
+            self.register_buffer(f"{name}_qweight", torch.zeros((E, n_in * w_bits // 32, n_out),
+                                                                dtype=torch.int32, device=device))
+            if mx:
+                setattr(self, f"{name}_qzeros", None)
+                self.register_buffer(f"{name}_scales", torch.full((E, G, n_out), 127,
+                                                                  dtype=torch.uint8, device=device))
+            else:
+                self.register_buffer(f"{name}_qzeros", torch.zeros((E, G, n_out * w_bits // 32),
+                                                                   dtype=torch.int32, device=device))
+                self.register_buffer(f"{name}_scales", torch.zeros((E, G, n_out), dtype=scale_dtype,
+                                                                   device=device))
+
+    @classmethod
+    def from_packed(cls, gate_up: dict, down: dict, w_bits: int = 4, group_size: int = -1,
+                    weight_format: str = "int", act_fn=None, device=None) -> "QuantExperts":
+        """From the two stacked entries (a checkpoint's, or ``quantize_model``'s
+        ``packed``): dicts of ``qweight`` (E, in*b/32, out), ``qzeros`` (None for
+        MXFP4) and ``scales``."""
+        if weight_format == "mxfp4":
+            w_bits = 4
+        E, nw, m2 = gate_up["qweight"].shape
+        H, I = nw * 32 // w_bits, m2 // 2
+        dev = device if device is not None else gate_up["qweight"].device
+        q = cls(E, H, I, w_bits, group_size, weight_format, scale_dtype=gate_up["scales"].dtype
+                if weight_format == "int" else torch.float16, act_fn=act_fn, device=dev)
+        for name, t in (("gate_up", gate_up), ("down", down)):
+            for k in ("qweight", "qzeros", "scales"):
+                buf = getattr(q, f"{name}_{k}")
+                if buf is None:
+                    continue
+                if t.get(k) is None or tuple(t[k].shape) != tuple(buf.shape) \
+                        or t[k].dtype != buf.dtype:
+                    raise ValueError(f"{name}.{k}: expected {buf.dtype} {tuple(buf.shape)}, got "
+                                     f"{None if t.get(k) is None else (t[k].dtype, tuple(t[k].shape))}")
+                buf.copy_(t[k])
+        return q
+
+    def extra_repr(self) -> str:
+        fmt = "format=mxfp4" if self.weight_format == "mxfp4" else \
+            f"bits={self.w_bits}, group_size={self.group_size}"
+        return (f"num_experts={self.num_experts}, hidden_dim={self.hidden_dim}, "
+                f"intermediate_dim={self.intermediate_dim}, {fmt}")
+
+    def dequantize(self, dtype: torch.dtype = torch.float16):
+        """The dense ``(gate_up_proj (E, 2I, H), down_proj (E, H, I))`` of `dtype`."""
+        out = []
+        for name in ("gate_up", "down"):
+            qw, qz, sc = (getattr(self, f"{name}_{k}") for k in ("qweight", "qzeros", "scales"))
+            out.append(torch.stack([
+                dequantize_packed_mx(qw[e], sc[e], dtype) if qz is None else
+                dequantize_packed(qw[e], qz[e], sc[e], self.w_bits, self.group_size, dtype)
+                for e in range(self.num_experts)]))
+        return tuple(out)
+
+    @torch.no_grad()
+    def forward(self, hidden_states: torch.Tensor, top_k_index: torch.Tensor,
+                top_k_weights: torch.Tensor) -> torch.Tensor:
+        require_cuda(hidden_states, "QuantExperts input")
+        H, I = self.hidden_dim, self.intermediate_dim
+        x = hidden_states.reshape(-1, H)
+        T = x.shape[0]
+        assert top_k_index.dim() == 2 and top_k_index.shape[0] == T \
+            and top_k_weights.shape == top_k_index.shape, "routing tensors must be (tokens, top_k)"
+        k = top_k_index.shape[1]
+        # assignment a = token * k + choice; slots are the assignments in expert order
+        flat = top_k_index.reshape(-1)
+        order = torch.argsort(flat, stable=True)
+        rows = torch.div(order, k, rounding_mode="floor").to(torch.int32)
+        # offsets[e] = number of assignments to experts below e.  (bincount + cumsum
+        # would give the same, but bincount on the device sizes its output from the
+        # data and so waits for it; searchsorted does not.)
+        offsets = torch.searchsorted(flat[order], torch.arange(
+            self.num_experts + 1, device=flat.device, dtype=flat.dtype)).to(torch.int32)
+        gu = qgemm_grouped(x, rows, offsets, self.gate_up_qweight, self.gate_up_qzeros,
+                           self.gate_up_scales, self.w_bits, self.group_size)
+        h = self.act_fn(gu[:, :I]) * gu[:, I:]
+        scale = top_k_weights.reshape(-1)[order].to(torch.float32)
+        d = qgemm_grouped(h, None, offsets, self.down_qweight, self.down_qzeros, self.down_scales,
+                          self.w_bits, self.group_size, row_scale=scale)
+        # token t's k slots through the inverse permutation, added in fp32 in choice
+        # order and rounded once (index_add_ would use atomics)
+        slot = torch.empty_like(order)
+        slot[order] = torch.arange(order.numel(), device=order.device)
+        d = d[slot].view(T, k, H)
+        acc = d[:, 0].to(torch.float32)
+        for j in range(1, k):
+            acc += d[:, j]
+        return acc.to(hidden_states.dtype).reshape(hidden_states.shape)

@@ -670,6 +670,56 @@ int tg_hadamard(void *stream, const void *X, int x_dtype, int64_t rows, int n, i
 int tg_hadamard_sym(void *stream, double *H, int n, int64_t stride_h, int block,
                     const int32_t *sign_bits);
 
+/* ---- A19: grouped packed GEMM (new; the expert layer of a Mixture-of-Experts
+ * model, on the reference's roadmap and served by neither side before) -----------
+ * E packed matrices of one shape (m x n), each applied to its own run of slots:
+ *   Y[i, r] = round(row_scale[i] * sum_k X[rows[i], k] * W^_e[r, k]),  r < m,
+ * for every slot i (0 <= i < R) of expert e, offsets[e] <= i < offsets[e + 1].
+ * offsets: E + 1 int32 in device memory, ascending, offsets[0] = 0, offsets[E] =
+ * R; empty experts are allowed.  rows: R int32 in device memory, rows[i] in
+ * [0, T) the row of X (T x n, x_dtype TG_F16 / TG_BF16, row stride stride_x >= n)
+ * that feeds slot i; a row may feed several slots.  rows is nullable: null means
+ * slot i reads row i, and then T must equal R.  row_scale: R f32 in device
+ * memory, nullable (null = 1).  There is no bias.  Nothing about the routing is
+ * read on the host: the call makes no synchronisation and no device-to-host
+ * copy, and its grid depends on R and E alone.  Values that break the contract
+ * (descending offsets, rows outside [0, T)) are clamped into the buffers on the
+ * device; the result is then unspecified but no access leaves X, Y or the
+ * workspace.
+ * Weights.  wfmt = 0, the integer bit stream (A14): qweight is E stacked images
+ * (E x n*b/32 x m), qzeros E x (G x m*b/32), scales E x (G x m) of scale_dtype
+ * TG_F16 / TG_F32; b = w_bits in {2, 3, 4, 8}, G = n/g, g = group or n when
+ * group <= 0.  wfmt = TG_FMT_MXFP4 (A15): qzeros is null, scales is E stacked
+ * E8M0 byte images (E x n/32 x m), group must be 32 and w_bits 4 (scale_dtype is
+ * ignored).  Every per-expert image is laid out exactly as tg_pack_codes /
+ * tg_pack_zeros / tg_pack_e8m0 write it.
+ * Numerics: W^_e is exactly tg_dequant_packed's (tg_dequant_mx's) output in
+ * x_dtype; products and sums are f32; row_scale is multiplied in f32 after the
+ * sum; one rounding to y_dtype (x_dtype or TG_F32); Y is R x m with row stride
+ * stride_y >= m.  No atomics: bit-identical from call to call.
+ * Requires n % 32 == 0, (m*b) % 32 == 0, g % 32 == 0 dividing n, 1 <= E <= 256,
+ * R >= 0.  R = 0 returns 0 at once; anything else is rejected with the
+ * argument's index before any device work.
+ * Two regimes, TG_QGROUPED = auto | rows | tiles (read per call).  rows (R <=
+ * 128, and what auto picks there): a workgroup of 64 features x 4 waves takes a
+ * run of up to 4 slots of one expert; K is split over S workgroups of at most 512
+ * values and over the waves; the partial sums [S][R][m] f32 go to the workspace
+ * and a second kernel adds them in ascending split order, multiplies by
+ * row_scale and rounds.  rows with R > 128 is an argument error (-8).  tiles
+ * (any R): an MFMA 16x16x32 tile kernel, (64 or 128 slots of one expert) x 64
+ * features per workgroup, 128-value K slabs unpacked into LDS beside the
+ * gathered X rows; no split-K, no workspace.  A workgroup never spans two
+ * experts; at most one partial tile per expert is wasted.
+ * tg_qgemm_grouped_workspace_size(R, E, m, n): S*R*m*4 bytes (+ alignment slack)
+ * for R <= 128, 0 above; ws may be null when the call takes the tiles regime. */
+size_t tg_qgemm_grouped_workspace_size(int R, int E, int m, int n);
+int tg_qgemm_grouped(void *stream, const void *X, int x_dtype, int T, int64_t stride_x,
+                     const int32_t *rows, const int32_t *offsets, int R, int E,
+                     const int32_t *qweight, const int32_t *qzeros, const void *scales,
+                     int scale_dtype, int wfmt, int m, int n, int group, int w_bits,
+                     const float *row_scale, void *Y, int y_dtype, int64_t stride_y, void *ws,
+                     size_t ws_bytes);
+
 #ifdef __cplusplus
 }
 #endif
