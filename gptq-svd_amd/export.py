@@ -274,22 +274,31 @@ def load_quantized(model: torch.nn.Module, path: str, device=None,
     ``desc_act=false`` configuration with supported bits, and every ``g_idx``
     must be the trivial ``arange(in) // group`` map (act-order checkpoints are
     out of scope).  `device`: where the model is moved (default: it stays).
-    `act_format`: a run-time choice for MXFP4 checkpoints, handed to every
-    ``MXQuantLinear`` (None: 16-bit activations; "mxfp8": the block-scaled W4A8
-    kernel); with an integer checkpoint it is an error.  The checkpoint does not
-    record it."""
-    from .qlinear import QuantLinear, _check_act_format
-    _check_act_format(act_format)
+    `act_format`: a run-time choice that the checkpoint does not record, handed
+    to every packed linear.  None: 16-bit activations.  "mxfp8": the block-scaled
+    W4A8 kernel of ``MXQuantLinear``, for MXFP4 checkpoints only.  "int8":
+    per-token INT8 activations on the i8 MFMA (``QuantLinear``), for integer
+    (``gptq_v2``) checkpoints only.  A format with the other kind of checkpoint,
+    an unknown format, and any format with a Mixture-of-Experts checkpoint are a
+    ``ValueError`` before any tensor is read."""
+    from .qlinear import ACT_FORMATS, INT_ACT_FORMATS, QuantLinear
     if act_format is not None:                   # before any tensor is read
+        known = sorted(ACT_FORMATS) + sorted(INT_ACT_FORMATS)
+        if not isinstance(act_format, str) or act_format not in known:
+            raise ValueError(f"act_format must be None or one of {known}, got {act_format!r}")
         with open(os.path.join(path, "quantize_config.json")) as f:
-            fmt = json.load(f).get("checkpoint_format", "gptq_v2")
-        if fmt != "mxfp4":
+            head = json.load(f)
+        fmt = head.get("checkpoint_format", "gptq_v2")
+        if act_format in ACT_FORMATS and fmt != "mxfp4":
             raise ValueError(f"act_format={act_format!r} needs an mxfp4 checkpoint; this one is "
                              f"{fmt!r}")
+        if act_format in INT_ACT_FORMATS and fmt != "gptq_v2":
+            raise ValueError(f"act_format={act_format!r} needs an integer (gptq_v2) checkpoint; "
+                             f"this one is {fmt!r}")
+        if head.get("experts"):
+            raise ValueError("act_format cannot be combined with a Mixture-of-Experts checkpoint "
+                             "(the grouped kernel takes 16-bit activations)")
     tensors, qc = read_quantized(path)
-    if act_format is not None and qc.get("experts"):
-        raise ValueError("act_format cannot be combined with a Mixture-of-Experts checkpoint "
-                         "(the grouped kernel takes 16-bit activations)")
     bits, group = int(qc["bits"]), int(qc["group_size"])
     blocks = _rotation_blocks(qc, tensors)
     if qc.get("checkpoint_format") == "mxfp4":
@@ -330,7 +339,8 @@ def load_quantized(model: torch.nn.Module, path: str, device=None,
             q = QuantLinear.from_packed(tensors[keys["qweight"]], tensors[keys["qzeros"]],
                                         tensors[keys["scales"]], bits, group, bias=bias,
                                         g_idx=tensors[keys["g_idx"]], device=lin.weight.device,
-                                        lowrank=lowrank, rotation=rotation)
+                                        lowrank=lowrank, rotation=rotation,
+                                        act_format=act_format)
         except ValueError as e:
             raise ValueError(f"{name}: {e}") from None
         if (q.out_features, q.in_features) != (lin.out_features, lin.in_features):

@@ -24,6 +24,12 @@ quantises x to e4m3 with one E8M0 byte per 32 columns (``quantize_act_mx``,
 ``tg_quant_act_mx``) and multiplies on the block-scaled MFMA instruction
 (``tg_qgemm_mx_act``): W4A8, different numerics from the weights-only path.
 
+INT8 activations (A20, opt-in): ``QuantLinear(..., act_format="int8")`` quantises
+x per token to int8 (``quantize_act_i8``, ``tg_quant_act_i8``) and multiplies the
+packed integer codes on the i8 MFMA (``tg_qgemm_act``): W4A8 (or W2/3/8A8), with
+the zero points applied once per group; different numerics from the weights-only
+path, and a run-time choice that the checkpoint does not record.
+
 Low-rank correction (A17, opt-in): a layer quantised with ``lowrank=r`` carries
 ``lr_a`` (out, r) and ``lr_b`` (r, in) beside its packed weight, and computes
 ``y = x W^^T + (x lr_b^T) lr_a^T + bias`` in three calls: the packed GEMM with
@@ -51,12 +57,12 @@ from typing import Optional
 import torch
 from torch import nn
 
-from ._lib import (ACT_FORMATS, DTYPES, TG_FMT_MXFP4, call, lib, ptr, require_cuda, stream,
-                   workspace)
+from ._lib import (ACT_FORMATS, DTYPES, INT_ACT_FORMATS, TG_FMT_MXFP4, call, lib, ptr,
+                   require_cuda, stream, workspace)
 
 __all__ = ["QuantLinear", "dequantize_packed", "MXQuantLinear", "dequantize_packed_mx",
            "quantize_act_mx", "dequantize_act_mx", "add_lowrank", "hadamard", "QuantExperts",
-           "qgemm_grouped"]
+           "qgemm_grouped", "INT_ACT_FORMATS", "quantize_act_i8", "dequantize_act_i8"]
 
 _BITS = (2, 3, 4, 8)
 
@@ -263,17 +269,61 @@ def add_lowrank(W: torch.Tensor, A: torch.Tensor, B: torch.Tensor,
     return out
 
 
+def _check_int_act_format(act_format) -> None:
+    if act_format is not None and (not isinstance(act_format, str)
+                                   or act_format not in INT_ACT_FORMATS):
+        raise ValueError(f"act_format must be None or one of {sorted(INT_ACT_FORMATS)} for an "
+                         f"integer checkpoint, got {act_format!r}")
+
+
+def quantize_act_i8(x: torch.Tensor):
+    """Per-token INT8 image of fp16 / bf16 activations (..., n), n % 32 == 0:
+    ``(xq int8 (..., n), xs float32 (...))`` with ``xs = max|x| / 127`` and
+    ``xq = rint(x / xs)`` in [-127, 127] (``tg_quant_act_i8``)."""
+    require_cuda(x, "quantize_act_i8 input")
+    if x.dtype not in (torch.float16, torch.bfloat16):
+        raise RuntimeError(f"quantize_act_i8 takes float16 or bfloat16, got {x.dtype}")
+    n = x.shape[-1]
+    if n == 0 or n % 32:
+        raise ValueError(f"quantize_act_i8 needs a last dim that is a multiple of 32, got {n}")
+    x2 = x.reshape(-1, n)
+    T = x2.shape[0]
+    xq = torch.empty((T, n), dtype=torch.int8, device=x.device)
+    xs = torch.empty((T,), dtype=torch.float32, device=x.device)
+    if T > 0:
+        if x2.stride(1) != 1 or (T > 1 and x2.stride(0) < n):
+            x2 = x2.contiguous()
+        ldx = x2.stride(0) if T > 1 else n
+        with torch.cuda.device(x.device):
+            call("tg_quant_act_i8", stream(), ptr(x2), DTYPES[x.dtype], T, ldx, n, 32, ptr(xq), n,
+                 ptr(xs), None)
+    return xq.reshape(*x.shape[:-1], n), xs.reshape(x.shape[:-1])
+
+
+def dequantize_act_i8(xq: torch.Tensor, xs: torch.Tensor,
+                      dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """``float(xq) * xs`` rounded once to `dtype` (plain torch)."""
+    return (xq.to(torch.float32) * xs.unsqueeze(-1)).to(dtype)
+
+
 class QuantLinear(nn.Module):
     """A linear layer whose weight stays packed.  The buffer names are the
     checkpoint's keys, so ``load_state_dict`` fills it.  ``module.to(dtype)``
     converts floating buffers like any module: fp32 ``scales`` become 16-bit
-    with it (and the decoded weight changes accordingly)."""
+    with it (and the decoded weight changes accordingly).
+    ``act_format=None``: weights only, the codes are decoded to x's dtype
+    (``tg_qgemm``).  ``act_format="int8"``: x is quantised per token to int8 per
+    call and both operands feed the i8 MFMA (``tg_qgemm_act``); a run-time choice
+    that the checkpoint does not record."""
 
     def __init__(self, in_features: int, out_features: int, w_bits: int, group_size: int,
                  bias: bool = False, scale_dtype: torch.dtype = torch.float16,
                  bias_dtype: torch.dtype = torch.float16, device=None, lowrank: int = 0,
-                 lowrank_dtype: torch.dtype = torch.float16, rotate_block: int = 0):
+                 lowrank_dtype: torch.dtype = torch.float16, rotate_block: int = 0,
+                 act_format=None):
         super().__init__()
+        _check_int_act_format(act_format)
+        self.act_format = act_format
         if w_bits not in _BITS:
             raise ValueError(f"w_bits must be one of {_BITS}, got {w_bits}")
         g = group_size if group_size > 0 else in_features
@@ -304,12 +354,12 @@ class QuantLinear(nn.Module):
     def from_packed(cls, qweight: torch.Tensor, qzeros: torch.Tensor, scales: torch.Tensor,
                     w_bits: int, group_size: int, bias: Optional[torch.Tensor] = None,
                     g_idx: Optional[torch.Tensor] = None, device=None,
-                    lowrank=None, rotation=None) -> "QuantLinear":
+                    lowrank=None, rotation=None, act_format=None) -> "QuantLinear":
         """From the packed tensors (a checkpoint's, or ``pack_quantized``'s).
         `g_idx`, when given, must be the trivial ``arange(in) // group``.
         ``lowrank=(A, B)``: the correction's factors, (out, r) and (r, in).
         ``rotation=(block, sign_bits)``: the packed weight is that of the rotated
-        basis and the forward rotates x first."""
+        basis and the forward rotates x first.  ``act_format``: None or "int8"."""
         m, n, g = _shapes(qweight, qzeros, scales, w_bits, group_size)
         if lowrank is not None:
             lowrank = _check_lowrank(lowrank, m, n)
@@ -325,7 +375,7 @@ class QuantLinear(nn.Module):
                 bias_dtype=bias.dtype if bias is not None else torch.float16, device=dev,
                 lowrank=lowrank[0].shape[1] if lowrank is not None else 0,
                 lowrank_dtype=lowrank[0].dtype if lowrank is not None else torch.float16,
-                rotate_block=rotation[0] if rotation is not None else 0)
+                rotate_block=rotation[0] if rotation is not None else 0, act_format=act_format)
         q.qweight.copy_(qweight)
         q.qzeros.copy_(qzeros)
         q.scales.copy_(scales)
@@ -342,6 +392,8 @@ class QuantLinear(nn.Module):
         lr = f", lowrank={self.lr_a.shape[1]}" if self.lr_a is not None else ""
         if self.rotate_block:
             lr += f", rotate_block={self.rotate_block}"
+        if self.act_format is not None:
+            lr += f", act_format={self.act_format}"
         return (f"in_features={self.in_features}, out_features={self.out_features}, "
                 f"bits={self.w_bits}, group_size={self.group_size}, "
                 f"bias={self.bias is not None}{lr}")
@@ -388,17 +440,28 @@ class QuantLinear(nn.Module):
                 x2, ldx = _rotate_rows(x2, T, n, ldx, self.rotate_block, self.had_sign), n
             bias = self.bias
             lr = self.lr_a is not None
-            # with a correction the GEMM leaves its fp32 sums; tg_lr_finish adds the bias
+            # with a correction the GEMM leaves its fp32 sums; tg_lr_finish adds the bias.
+            # Z = x lr_b^T always comes from the 16-bit x, under act_format too.
             out = torch.empty((T, m), dtype=torch.float32, device=x.device) if lr else y
             gb = None if lr else bias
             with torch.cuda.device(x.device):
-                nbytes = lib.tg_qgemm_workspace_size(T, m, n)
-                ws = workspace(nbytes, x.device)
-                call("tg_qgemm", stream(), ptr(x2), DTYPES[x.dtype], T, ldx, ptr(self.qweight),
-                     ptr(self.qzeros), ptr(self.scales), DTYPES[self.scales.dtype], m, n,
-                     self.group_size, self.w_bits, ptr(gb),
-                     DTYPES[gb.dtype] if gb is not None else 0, ptr(out), DTYPES[out.dtype], m,
-                     ptr(ws), nbytes)
+                if self.act_format is not None:
+                    nbytes = lib.tg_qgemm_act_workspace_size(T, m, n, self.group_size)
+                    ws = workspace(nbytes, x.device)
+                    call("tg_qgemm_act", stream(), ptr(x2), DTYPES[x.dtype], T, ldx,
+                         ptr(self.qweight), ptr(self.qzeros), ptr(self.scales),
+                         DTYPES[self.scales.dtype], m, n, self.group_size, self.w_bits,
+                         INT_ACT_FORMATS[self.act_format], ptr(gb),
+                         DTYPES[gb.dtype] if gb is not None else 0, ptr(out), DTYPES[out.dtype], m,
+                         ptr(ws), nbytes)
+                else:
+                    nbytes = lib.tg_qgemm_workspace_size(T, m, n)
+                    ws = workspace(nbytes, x.device)
+                    call("tg_qgemm", stream(), ptr(x2), DTYPES[x.dtype], T, ldx,
+                         ptr(self.qweight), ptr(self.qzeros), ptr(self.scales),
+                         DTYPES[self.scales.dtype], m, n, self.group_size, self.w_bits, ptr(gb),
+                         DTYPES[gb.dtype] if gb is not None else 0, ptr(out), DTYPES[out.dtype], m,
+                         ptr(ws), nbytes)
                 if lr:
                     _lowrank_finish(x2, T, ldx, out, self.lr_a, self.lr_b, bias, y)
         return y.reshape(*x.shape[:-1], m)

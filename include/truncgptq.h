@@ -555,7 +555,7 @@ int tg_qgemm_mx(void *stream, const void *X, int x_dtype, int T, int64_t stride_
  * to 128 (2048 + 64 bytes per 16 rows x 128 columns; the kernel keeps it in the
  * instruction's operand order), plus S*T*m*4 bytes when S > 1, plus alignment
  * slack; ws is never null. */
-enum tg_act_format { TG_ACT_MXFP8 = 1 };
+enum tg_act_format { TG_ACT_MXFP8 = 1, TG_ACT_INT8 = 2 /* A20, tg_qgemm_act */ };
 int tg_quant_act_mx(void *stream, const void *X, int x_dtype, int T, int64_t stride_x, int n,
                     int act_fmt, uint8_t *xq, int64_t stride_q, uint8_t *xs);
 size_t tg_qgemm_mx_act_workspace_size(int T, int m, int n);
@@ -719,6 +719,59 @@ int tg_qgemm_grouped(void *stream, const void *X, int x_dtype, int T, int64_t st
                      int scale_dtype, int wfmt, int m, int n, int group, int w_bits,
                      const float *row_scale, void *Y, int y_dtype, int64_t stride_y, void *ws,
                      size_t ws_bytes);
+
+/* ---- A20: INT8 activations (new; opt-in W4A8 / W8A8 for integer checkpoints) ---
+ * The A14 image (qweight, qzeros, scales; b in {2, 3, 4, 8}) multiplied on the
+ * i8 MFMA against per-token INT8 activations.  `act_fmt` must be TG_ACT_INT8
+ * (tg_qgemm_mx_act keeps taking TG_ACT_MXFP8 only).  Every f32 operation below is
+ * one correctly rounded operation.  Activations are finite; NaN and Inf are
+ * outside the contract.
+ *
+ * Quantiser (tg_quant_act_i8; X is T x n of x_dtype TG_F16 / TG_BF16 with row
+ * stride stride_x >= n, n % 32 == 0), per token and symmetric:
+ *   a = max_k |x[t, k]|, converted exactly to f32;  xs[t] = a / 127.f;
+ *   q[t, k] = clamp(rint(x[t, k] / xs[t]), -127, 127), ties to even; -128 is
+ *     never written; a row with a == 0 gives xs = 0 and q = 0;
+ *   xsum[t, j] = sum of q[t, k] over group j (int32, T x G contiguous, nullable
+ *     here), G = n / g, g = group or n when group <= 0.
+ * xq is T x n int8 with row stride stride_q >= n, xs is T f32.  Loads of X are
+ * 16 bytes wide where X and stride_x allow it and scalar otherwise, the stores
+ * of xq likewise.
+ *
+ * tg_qgemm_act: with off = 128 for w_bits == 8 and 0 otherwise, c' = code_u -
+ * off, z' = zero_u - off,
+ *   D[t, j, r] = sum_{k in group j} q[t, k] c'[r, k] - z'[j, r] xsum[t, j]
+ * (exact in int32: the zero point never enters the inner loop, and c' - z', which
+ * spans +-255 at 8 bits, is never formed), and
+ *   Y[t, r] = round(xs[t] * sum_j float(D[t, j, r]) * float(scale[j, r]) + bias[r]):
+ * the sum over j in f32 in ascending j (float(D) * scale may be contracted with
+ * its add), then one multiply by xs[t], the bias (m, nullable, TG_F16 / TG_BF16 /
+ * TG_F32) added in f32, one rounding to y_dtype TG_F16 / TG_BF16 / TG_F32.  The
+ * weight this multiplies by is exactly tg_dequant_packed's TG_F32 output.
+ * Bit-identical from call to call (no floating-point atomics).
+ * Requires n % 32 == 0, g % 32 == 0 dividing n, (m * b) % 32 == 0, g <= 65536
+ * (255 * 127 * g stays below 2^31) and G <= 8192; scale_dtype TG_F16 / TG_F32;
+ * x_dtype TG_F16 / TG_BF16.  Anything else is rejected with the argument's index
+ * before any device work.
+ * One regime for every T: the quantiser writes X^ into the workspace in the MFMA
+ * operand's order, then a workgroup owns (16 rows up to T = 32, above 64) x 64
+ * features and walks K in steps of 64 (v_mfma_i32_16x16x64_i8; two
+ * v_mfma_i32_16x16x32_i8 a step when g % 64 == 32, so that no instruction mixes
+ * two groups).  While the output tiles are fewer than ~512 workgroups K is split
+ * at group boundaries into S parts of at least 4 steps; the partial sums
+ * [S][T][m] f32 are added in ascending order by a second kernel, which then
+ * applies xs and the bias.  Per-channel weights (one group) are never split.
+ * tg_qgemm_act_workspace_size(T, m, n, group): X^ (1 KB per 16 rows x 64
+ * columns), xs, xsum (T rounded up to 16), plus S*T*m*4 bytes when S > 1, plus
+ * alignment slack; 0 for arguments the GEMM would reject.  ws is never null. */
+int tg_quant_act_i8(void *stream, const void *X, int x_dtype, int T, int64_t stride_x, int n,
+                    int group, int8_t *xq, int64_t stride_q, float *xs, int32_t *xsum);
+size_t tg_qgemm_act_workspace_size(int T, int m, int n, int group);
+int tg_qgemm_act(void *stream, const void *X, int x_dtype, int T, int64_t stride_x,
+                 const int32_t *qweight, const int32_t *qzeros, const void *scales,
+                 int scale_dtype, int m, int n, int group, int w_bits, int act_fmt,
+                 const void *bias, int bias_dtype, void *Y, int y_dtype, int64_t stride_y,
+                 void *ws, size_t ws_bytes);
 
 #ifdef __cplusplus
 }

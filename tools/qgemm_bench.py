@@ -23,6 +23,11 @@ beside the weights-only tg_qgemm_mx, the dense fp16 matmul and the activation
 quantiser alone, alternating inside every run (eager launches); --other-lib
 adds tg_qgemm_mx and tg_qgemm of another build of the library, alternating too.
 
+--act int8 (integer format) times the W4A8 path tg_qgemm_act, quantiser included,
+beside the weights-only tg_qgemm and the dense fp16 matmul, alternating inside
+every run, at m x n = 4096 x 4096 and 14336 x 4096; the sweep is taken twice.
+
+    python tools/qgemm_bench.py --act int8 --T 1 16 64 512 4096 --out profiles/qlinear/qiact.json
     python tools/qgemm_bench.py [--graph] [--format int|mxfp4] [--group G] [--out FILE]
     python tools/qgemm_bench.py --format mxfp4 --act mxfp8 [--other-lib SO] [--out FILE]
 """
@@ -204,6 +209,69 @@ def main_act(args):
     print("wrote", args.out)
 
 
+def main_iact(args):
+    """--act int8 (integer format, 4-bit, --group): tg_qgemm_act, its quantiser
+    launch included, beside the weights-only tg_qgemm on the same packed tensors
+    and the dense fp16 matmul, alternating inside every run.  The whole sweep is
+    taken twice; a row holds both medians of every path and the speed-up over the
+    weights-only kernel from each."""
+    gen = torch.Generator().manual_seed(0)
+    flush = torch.empty(1 << 30, dtype=torch.uint8, device=DEV)
+    rows = {}
+    for rep in range(2):
+        for m, n in ((4096, 4096), (14336, 4096)):
+            qw, qz, sc = random_packed(m, n, gen, "int")
+            dense = dequantize_packed(qw, qz, sc, BITS, GROUP, torch.float16)
+            packed_bytes = qw.numel() * 4 + qz.numel() * 4 + sc.numel() * 2
+            pc = -(-ROTATE_BYTES // packed_bytes)
+            dc = -(-ROTATE_BYTES // (dense.numel() * 2))
+            packs = [(qw, qz, sc)] + [(qw.clone(), qz.clone(), sc.clone()) for _ in range(pc - 1)]
+            denses = [dense] + [dense.clone() for _ in range(dc - 1)]
+            for T in args.T:
+                x = torch.randn(T, n, generator=gen).to(torch.float16).to(DEV)
+                y = torch.empty(T, m, dtype=torch.float16, device=DEV)
+                nb_w = L.lib.tg_qgemm_workspace_size(T, m, n)
+                nb_a = L.lib.tg_qgemm_act_workspace_size(T, m, n, GROUP)
+                ws_w, ws_a = L.workspace(nb_w, DEV), L.workspace(nb_a, DEV)
+
+                def head(i):
+                    a, b, c = packs[i]
+                    return (L.stream(), L.ptr(x), L.TG_F16, T, n, L.ptr(a), L.ptr(b), L.ptr(c),
+                            L.TG_F16, m, n, GROUP, BITS)
+
+                def tail(ws, nb):
+                    return (None, 0, L.ptr(y), L.TG_F16, m, L.ptr(ws), nb)
+
+                paths = {"act": (lambda i: L.call("tg_qgemm_act", *head(i), L.TG_ACT_INT8,
+                                                  *tail(ws_a, nb_a)), pc),
+                         "weights_only": (lambda i: L.call("tg_qgemm", *head(i),
+                                                           *tail(ws_w, nb_w)), pc),
+                         "dense": (lambda i: torch.nn.functional.linear(x, denses[i]), dc)}
+                t = timed_alternating(paths, flush, args.warmup, args.runs)
+                paths["act"][0](0)
+                ref = torch.nn.functional.linear(x, dense).float()
+                row = rows.setdefault((m, n, T), dict(
+                    m=m, n=n, T=T, packed_copies=pc, dense_copies=dc,
+                    rel_diff_vs_dense=float((y.float() - ref).norm() / ref.norm())))
+                for k, (med, _) in t.items():
+                    row.setdefault(k + "_ms", []).append(med)
+                row.setdefault("speedup_vs_weights_only", []).append(
+                    t["weights_only"][0] / t["act"][0])
+                row.setdefault("act_TOPs", []).append(2.0 * T * m * n / (t["act"][0] * 1e-3) / 1e12)
+                print(json.dumps(dict(rep=rep, **row)), flush=True)
+            del packs, denses
+    out = dict(device=torch.cuda.get_device_name(0), format="int", bits=BITS, group=GROUP,
+               act="int8", dtype="float16", runs=args.runs, warmup=args.warmup, launch="eager",
+               method="HIP events around one call on each of >= 768 MB of weight copies, "
+                      "per-call median; 1 GiB overwritten before every bracket; the paths "
+                      "alternate inside every run; every figure is a pair, one per whole sweep",
+               rows=list(rows.values()))
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+    print("wrote", args.out)
+
+
 def main():
     global GROUP
     ap = argparse.ArgumentParser()
@@ -215,17 +283,20 @@ def main():
                     help="time a captured graph of the calls instead of eager launches")
     ap.add_argument("--format", choices=["int", "mxfp4"], default="int")
     ap.add_argument("--group", type=int, default=GROUP, help="integer group size (format int)")
-    ap.add_argument("--act", choices=["mxfp8"], default=None,
-                    help="with --format mxfp4: time tg_qgemm_mx_act beside the other paths")
+    ap.add_argument("--act", choices=["mxfp8", "int8"], default=None,
+                    help="mxfp8 (with --format mxfp4): time tg_qgemm_mx_act beside the other "
+                         "paths; int8 (integer format): tg_qgemm_act likewise")
     ap.add_argument("--other-lib", default=None,
                     help="with --act: another build of libtruncgptq.so to time against")
     args = ap.parse_args()
     mx = args.format == "mxfp4"
     GROUP = 32 if mx else args.group
-    if args.act and not mx:
-        raise SystemExit("--act needs --format mxfp4")
+    if (args.act == "mxfp8") != mx and args.act:
+        raise SystemExit("--act mxfp8 needs --format mxfp4, --act int8 the integer format")
     if not torch.cuda.is_available():
         raise SystemExit("qgemm_bench needs the GPU (there is nothing to time without one)")
+    if args.act == "int8":
+        return main_iact(args)
     if args.act:
         return main_act(args)
     gen = torch.Generator().manual_seed(0)
