@@ -1,6 +1,8 @@
-// Shared by the packed-inference files (qlinear.hip, qmxact.hip): the 16-bit
-// operand / output types as raw bits, and the split-K reduction that finishes
-// both files' partial sums.
+// Shared by the packed-inference files (qlinear.hip, qmxact.hip, qiact.hip,
+// qgrouped.hip, lrinfer.hip): the 16-bit operand / output types as raw bits,
+// and the split-K reduction that finishes the partial sums of qlinear.hip,
+// qmxact.hip and lrinfer.hip (bias only; qgrouped.hip and qiact.hip, which
+// scale the rows, have their own).
 #pragma once
 #include <hip/hip_bf16.h>
 #include <hip/hip_fp16.h>

@@ -451,8 +451,6 @@ int qgrouped_mode() {
   return 0;
 }
 
-bool bits_ok(int b) { return b == 2 || b == 3 || b == 4 || b == 8; }
-
 }  // namespace
 
 // ===========================================================================
@@ -522,12 +520,7 @@ extern "C" int tg_qgemm_grouped(void *stream, const void *X, int x_dtype, int T,
     TG_WS(arena);
     const dim3 grid(ftiles, S, int(tile_bound(R, E, RW_RUN)));
     if (mx) launch_rows<4, FMT_MX>(c, grid, ub, part);
-    else switch (w_bits) {
-      case 2: launch_rows<2, FMT_INT>(c, grid, ub, part); break;
-      case 3: launch_rows<3, FMT_INT>(c, grid, ub, part); break;
-      case 4: launch_rows<4, FMT_INT>(c, grid, ub, part); break;
-      default: launch_rows<8, FMT_INT>(c, grid, ub, part); break;
-    }
+    else with_bits(w_bits, [&](auto b) { launch_rows<b.value, FMT_INT>(c, grid, ub, part); });
     TG_LAUNCHED();
     hipLaunchKernelGGL(qgrouped_reduce_kernel, dim3(tg::cdiv(int64_t(R) * m, 256)), dim3(256), 0,
                        c.st, part, S, R, m, row_scale, Y, y_dtype, stride_y);
@@ -539,12 +532,7 @@ extern "C" int tg_qgemm_grouped(void *stream, const void *X, int x_dtype, int T,
   const dim3 grid(unsigned(tile_bound(R, E, BM)), ftiles);
   const int xvec = (reinterpret_cast<uintptr_t>(X) % 16 == 0 && stride_x % 8 == 0) ? 1 : 0;
   if (mx) launch_tiles<4, FMT_MX>(c, grid, BM, xvec);
-  else switch (w_bits) {
-    case 2: launch_tiles<2, FMT_INT>(c, grid, BM, xvec); break;
-    case 3: launch_tiles<3, FMT_INT>(c, grid, BM, xvec); break;
-    case 4: launch_tiles<4, FMT_INT>(c, grid, BM, xvec); break;
-    default: launch_tiles<8, FMT_INT>(c, grid, BM, xvec); break;
-  }
+  else with_bits(w_bits, [&](auto b) { launch_tiles<b.value, FMT_INT>(c, grid, BM, xvec); });
   TG_LAUNCHED();
   return 0;
 }

@@ -424,8 +424,6 @@ __global__ __launch_bounds__(256) void iact_reduce_kernel(const float *__restric
   store_from_float(Y, y_dt, int64_t(t) * ldy + r, v);
 }
 
-bool bits_ok(int b) { return b == 2 || b == 3 || b == 4 || b == 8; }
-
 int act_rows(int T) { return T <= IA_SMALL_T ? 16 : 64; }
 
 // g % 64 == 32: a group boundary falls inside a step
@@ -537,12 +535,9 @@ extern "C" int tg_qgemm_act(void *stream, const void *X, int x_dtype, int T, int
   TG_WS(arena);
   hipStream_t st = (hipStream_t)stream;
   const bool split = split_step(g);
-  switch (w_bits) {
-    case 2: launch_quant<2>(st, X, x_dtype, T, stride_x, n, g, split, l.xq, n, l.xs, l.xsum); break;
-    case 3: launch_quant<3>(st, X, x_dtype, T, stride_x, n, g, split, l.xq, n, l.xs, l.xsum); break;
-    case 4: launch_quant<4>(st, X, x_dtype, T, stride_x, n, g, split, l.xq, n, l.xs, l.xsum); break;
-    default: launch_quant<8>(st, X, x_dtype, T, stride_x, n, g, split, l.xq, n, l.xs, l.xsum);
-  }
+  with_bits(w_bits, [&](auto b) {
+    launch_quant<b.value>(st, X, x_dtype, T, stride_x, n, g, split, l.xq, n, l.xs, l.xsum);
+  });
   TG_LAUNCHED();
   const dim3 grid(tg::cdiv(m, IA_TILE), tg::cdiv(T, BM), l.S);
   const uint32_t *qw = reinterpret_cast<const uint32_t *>(qweight);
@@ -556,18 +551,10 @@ extern "C" int tg_qgemm_act(void *stream, const void *X, int x_dtype, int T, int
     if (BM == 16) TG_IA(B_, SP_, 1, 1, 1, 4); \
     else TG_IA(B_, SP_, 2, 2, 2, 2);      \
   } while (0)
-#define TG_IA_BITS(B_)                \
-  do {                                \
-    if (split) TG_IA_TILE(B_, true);  \
-    else TG_IA_TILE(B_, false);       \
-  } while (0)
-  switch (w_bits) {
-    case 2: TG_IA_BITS(2); break;
-    case 3: TG_IA_BITS(3); break;
-    case 4: TG_IA_BITS(4); break;
-    default: TG_IA_BITS(8);
-  }
-#undef TG_IA_BITS
+  with_bits(w_bits, [&](auto b) {
+    if (split) TG_IA_TILE(b.value, true);
+    else TG_IA_TILE(b.value, false);
+  });
 #undef TG_IA_TILE
 #undef TG_IA
   TG_LAUNCHED();

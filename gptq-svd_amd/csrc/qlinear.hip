@@ -394,8 +394,6 @@ int qgemm_mode() {
   return 0;
 }
 
-bool bits_ok(int b) { return b == 2 || b == 3 || b == 4 || b == 8; }
-
 }  // namespace
 
 // ===========================================================================
@@ -425,16 +423,10 @@ extern "C" int tg_dequant_packed(void *stream, const int32_t *qweight, const int
   hipStream_t st = (hipStream_t)stream;
   const uint32_t *qw = reinterpret_cast<const uint32_t *>(qweight);
   const uint32_t *qz = reinterpret_cast<const uint32_t *>(qzeros);
-#define TG_DQ(b)                                                                              \
-  hipLaunchKernelGGL(dequant_kernel<b>, grid, dim3(256), 0, st, qw, qz, scales, scale_dtype, m, \
-                     n, g, out, out_dtype, ldo)
-  switch (w_bits) {
-    case 2: TG_DQ(2); break;
-    case 3: TG_DQ(3); break;
-    case 4: TG_DQ(4); break;
-    default: TG_DQ(8); break;
-  }
-#undef TG_DQ
+  with_bits(w_bits, [&](auto b) {
+    hipLaunchKernelGGL(dequant_kernel<b.value>, grid, dim3(256), 0, st, qw, qz, scales, scale_dtype,
+                       m, n, g, out, out_dtype, ldo);
+  });
   TG_LAUNCHED();
   return 0;
 }
@@ -515,12 +507,9 @@ static int qgemm_run(const QgemmIdx &ix, int fmt, void *stream, const void *X, i
     TG_ARG(S <= 65535, ix.n, "n too large");
     if (fmt == FMT_MX)
       launch_gemv_b<4, FMT_MX>(st, x_dtype, TT, grid, Xp, T, ldx, qw, qz, scales, scale_dtype, m, n, g, ub, part);
-    else switch (w_bits) {
-      case 2: launch_gemv_b<2>(st, x_dtype, TT, grid, Xp, T, ldx, qw, qz, scales, scale_dtype, m, n, g, ub, part); break;
-      case 3: launch_gemv_b<3>(st, x_dtype, TT, grid, Xp, T, ldx, qw, qz, scales, scale_dtype, m, n, g, ub, part); break;
-      case 4: launch_gemv_b<4>(st, x_dtype, TT, grid, Xp, T, ldx, qw, qz, scales, scale_dtype, m, n, g, ub, part); break;
-      default: launch_gemv_b<8>(st, x_dtype, TT, grid, Xp, T, ldx, qw, qz, scales, scale_dtype, m, n, g, ub, part); break;
-    }
+    else with_bits(w_bits, [&](auto b) {
+      launch_gemv_b<b.value>(st, x_dtype, TT, grid, Xp, T, ldx, qw, qz, scales, scale_dtype, m, n, g, ub, part);
+    });
     TG_LAUNCHED();
     hipLaunchKernelGGL(qgemv_reduce_kernel, dim3(tg::cdiv(int64_t(T) * m, 256)), dim3(256), 0, st,
                        part, S, T, m, bias, bias_dtype, Y, y_dtype, ldy);
@@ -540,19 +529,13 @@ static int qgemm_run(const QgemmIdx &ix, int fmt, void *stream, const void *X, i
   }
   const dim3 grid(tg::cdiv(m, MF_TILE), tg::cdiv(T, mfma_rows(T)), S);
   const int xvec = (reinterpret_cast<uintptr_t>(X) % 16 == 0 && ldx % 8 == 0) ? 1 : 0;
-#define TG_MF(b)                                                                               \
-  launch_mfma_b<b>(st, x_dtype, grid, Xp, T, ldx, xvec, qw, qz, scales, scale_dtype, m, n, g, sps, \
-                   part, bias, bias_dtype, Y, y_dtype, ldy)
   if (fmt == FMT_MX)
     launch_mfma_b<4, FMT_MX>(st, x_dtype, grid, Xp, T, ldx, xvec, qw, qz, scales, scale_dtype, m, n, g,
                              sps, part, bias, bias_dtype, Y, y_dtype, ldy);
-  else switch (w_bits) {
-    case 2: TG_MF(2); break;
-    case 3: TG_MF(3); break;
-    case 4: TG_MF(4); break;
-    default: TG_MF(8); break;
-  }
-#undef TG_MF
+  else with_bits(w_bits, [&](auto b) {
+    launch_mfma_b<b.value>(st, x_dtype, grid, Xp, T, ldx, xvec, qw, qz, scales, scale_dtype, m, n, g,
+                           sps, part, bias, bias_dtype, Y, y_dtype, ldy);
+  });
   TG_LAUNCHED();
   if (S > 1) {
     hipLaunchKernelGGL(qgemv_reduce_kernel, dim3(tg::cdiv(int64_t(T) * m, 256)), dim3(256), 0, st,

@@ -1,11 +1,30 @@
 // Shared by the packed GEMMs that unpack weights themselves (qlinear.hip,
 // qgrouped.hip): the AutoGPTQ bit stream and the MXFP4 pair decoded one unit of
 // 32 values at a time, and the 16x16x32 MFMA on raw 16-bit operands.  The
-// layouts are described at the top of qlinear.hip.
+// layouts are described at the top of qlinear.hip.  qiact.hip takes the bit
+// stream and the host's choice of code width from here too.
 #pragma once
+#include <type_traits>
+
 #include "qdtype.h"
 
 namespace {
+
+// ---- the code widths (host) ---------------------------------------------------
+inline bool bits_ok(int b) { return b == 2 || b == 3 || b == 4 || b == 8; }
+
+// f(std::integral_constant<int, B>{}) for the run-time w_bits, so that B can
+// pick a template instance.  Callers have checked bits_ok; any other width
+// runs as 8.
+template <class F>
+inline void with_bits(int w_bits, F &&f) {
+  switch (w_bits) {
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    default: f(std::integral_constant<int, 8>{}); break;
+  }
+}
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));

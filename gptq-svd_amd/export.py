@@ -281,7 +281,7 @@ def load_quantized(model: torch.nn.Module, path: str, device=None,
     (``gptq_v2``) checkpoints only.  A format with the other kind of checkpoint,
     an unknown format, and any format with a Mixture-of-Experts checkpoint are a
     ``ValueError`` before any tensor is read."""
-    from .qlinear import ACT_FORMATS, INT_ACT_FORMATS, QuantLinear
+    from .qlinear import ACT_FORMATS, INT_ACT_FORMATS, MXQuantLinear, QuantLinear
     if act_format is not None:                   # before any tensor is read
         known = sorted(ACT_FORMATS) + sorted(INT_ACT_FORMATS)
         if not isinstance(act_format, str) or act_format not in known:
@@ -302,30 +302,59 @@ def load_quantized(model: torch.nn.Module, path: str, device=None,
     bits, group = int(qc["bits"]), int(qc["group_size"])
     blocks = _rotation_blocks(qc, tensors)
     if qc.get("checkpoint_format") == "mxfp4":
-        return _load_mx(model, tensors, qc, device, act_format, blocks)
-    if bits not in (2, 3, 4, 8):
-        raise ValueError(f"quantize_config.json: bits={bits} is not one of 2, 3, 4, 8")
-    if qc.get("desc_act", False):
-        raise ValueError("quantize_config.json: desc_act=true (act-order) checkpoints are not "
-                         "supported")
-    if not isinstance(qc.get("sym"), bool):
-        raise ValueError("quantize_config.json: sym must be true or false")
-    fmt = qc.get("checkpoint_format", "gptq_v2")
-    if fmt != "gptq_v2":
-        raise ValueError(f"quantize_config.json: checkpoint_format={fmt!r}; only gptq_v2 (true "
-                         "zero points) and mxfp4 are supported")
-    names = [k[:-len(".qweight")] for k in tensors if k.endswith(".qweight")]
+        if bits != 4 or group != 32:
+            raise ValueError(f"quantize_config.json: mxfp4 needs bits=4 and group_size=32, got "
+                             f"bits={qc['bits']}, group_size={qc['group_size']}")
+        if qc.get("desc_act", False):
+            raise ValueError("quantize_config.json: desc_act=true (act-order) checkpoints are not "
+                             "supported")
+        required = ("scales",)
+
+        def build(t, keys, bias, lowrank, rotation, dev):
+            return MXQuantLinear.from_packed(t[keys["qweight"]], t[keys["scales"]], bias=bias,
+                                             device=dev, act_format=act_format, lowrank=lowrank,
+                                             rotation=rotation)
+    else:
+        if bits not in (2, 3, 4, 8):
+            raise ValueError(f"quantize_config.json: bits={bits} is not one of 2, 3, 4, 8")
+        if qc.get("desc_act", False):
+            raise ValueError("quantize_config.json: desc_act=true (act-order) checkpoints are not "
+                             "supported")
+        if not isinstance(qc.get("sym"), bool):
+            raise ValueError("quantize_config.json: sym must be true or false")
+        fmt = qc.get("checkpoint_format", "gptq_v2")
+        if fmt != "gptq_v2":
+            raise ValueError(f"quantize_config.json: checkpoint_format={fmt!r}; only gptq_v2 "
+                             "(true zero points) and mxfp4 are supported")
+        required = ("qzeros", "scales", "g_idx")
+
+        def build(t, keys, bias, lowrank, rotation, dev):
+            return QuantLinear.from_packed(t[keys["qweight"]], t[keys["qzeros"]], t[keys["scales"]],
+                                           bits, group, bias=bias, g_idx=t[keys["g_idx"]],
+                                           device=dev, lowrank=lowrank, rotation=rotation,
+                                           act_format=act_format)
     used = set()
     _load_experts(model, tensors, qc, used)
-    for name in names:
+    _load_linears(model, tensors, used, blocks, required, build)
+    return _load_rest(model, tensors, used, device)
+
+
+def _load_linears(model: torch.nn.Module, tensors: Dict[str, torch.Tensor], used: set,
+                  blocks: Dict[str, int], required, build) -> None:
+    """Every ``nn.Linear`` with a ``<name>.qweight`` in the checkpoint becomes
+    the packed module that ``build(tensors, keys, bias, lowrank, rotation,
+    device)`` makes of it (the format's one ``from_packed`` call); `required`
+    names the tensors besides ``qweight`` that the format cannot do without, and
+    `used` gains the tensors taken."""
+    for name in [k[:-len(".qweight")] for k in tensors if k.endswith(".qweight")]:
         try:
             lin = model.get_submodule(name)
         except AttributeError:
             raise KeyError(f"{name}: packed in the checkpoint but absent from the model") from None
         if not isinstance(lin, torch.nn.Linear):
             raise TypeError(f"{name}: expected nn.Linear, found {type(lin).__name__}")
-        keys = {k: f"{name}.{k}" for k in ("qweight", "qzeros", "scales", "g_idx", "bias")}
-        for k in ("qzeros", "scales", "g_idx"):
+        keys = {k: f"{name}.{k}" for k in ("qweight", *required, "bias")}
+        for k in required:
             if keys[k] not in tensors:
                 raise KeyError(f"{keys[k]} is missing from the checkpoint")
         bias = tensors.get(keys["bias"])
@@ -336,11 +365,7 @@ def load_quantized(model: torch.nn.Module, path: str, device=None,
         lowrank = _lowrank_of(tensors, name, keys)
         rotation = _rotation_of(tensors, name, blocks, keys)
         try:
-            q = QuantLinear.from_packed(tensors[keys["qweight"]], tensors[keys["qzeros"]],
-                                        tensors[keys["scales"]], bits, group, bias=bias,
-                                        g_idx=tensors[keys["g_idx"]], device=lin.weight.device,
-                                        lowrank=lowrank, rotation=rotation,
-                                        act_format=act_format)
+            q = build(tensors, keys, bias, lowrank, rotation, lin.weight.device)
         except ValueError as e:
             raise ValueError(f"{name}: {e}") from None
         if (q.out_features, q.in_features) != (lin.out_features, lin.in_features):
@@ -348,52 +373,6 @@ def load_quantized(model: torch.nn.Module, path: str, device=None,
                              f"model's linear is {lin.out_features} x {lin.in_features}")
         _set_submodule(model, name, q)
         used.update(v for v in keys.values() if v in tensors)
-    return _load_rest(model, tensors, used, device)
-
-
-def _load_mx(model: torch.nn.Module, tensors: Dict[str, torch.Tensor], qc: Dict[str, Any],
-             device, act_format=None, blocks=None) -> torch.nn.Module:
-    """load_quantized for ``checkpoint_format: "mxfp4"``: every ``nn.Linear``
-    with a ``<name>.qweight`` becomes a ``qlinear.MXQuantLinear``."""
-    from .qlinear import MXQuantLinear
-    if int(qc["bits"]) != 4 or int(qc["group_size"]) != 32:
-        raise ValueError(f"quantize_config.json: mxfp4 needs bits=4 and group_size=32, got "
-                         f"bits={qc['bits']}, group_size={qc['group_size']}")
-    if qc.get("desc_act", False):
-        raise ValueError("quantize_config.json: desc_act=true (act-order) checkpoints are not "
-                         "supported")
-    used = set()
-    _load_experts(model, tensors, qc, used)
-    for name in [k[:-len(".qweight")] for k in tensors if k.endswith(".qweight")]:
-        try:
-            lin = model.get_submodule(name)
-        except AttributeError:
-            raise KeyError(f"{name}: packed in the checkpoint but absent from the model") from None
-        if not isinstance(lin, torch.nn.Linear):
-            raise TypeError(f"{name}: expected nn.Linear, found {type(lin).__name__}")
-        keys = {k: f"{name}.{k}" for k in ("qweight", "scales", "bias")}
-        if keys["scales"] not in tensors:
-            raise KeyError(f"{keys['scales']} is missing from the checkpoint")
-        bias = tensors.get(keys["bias"])
-        if (bias is None) != (lin.bias is None):
-            raise ValueError(f"{name}: the checkpoint and the model disagree about a bias")
-        if bias is not None:
-            bias = bias.to(lin.bias.dtype)
-        lowrank = _lowrank_of(tensors, name, keys)
-        rotation = _rotation_of(tensors, name, blocks or {}, keys)
-        try:
-            q = MXQuantLinear.from_packed(tensors[keys["qweight"]], tensors[keys["scales"]],
-                                          bias=bias, device=lin.weight.device,
-                                          act_format=act_format, lowrank=lowrank,
-                                          rotation=rotation)
-        except ValueError as e:
-            raise ValueError(f"{name}: {e}") from None
-        if (q.out_features, q.in_features) != (lin.out_features, lin.in_features):
-            raise ValueError(f"{name}: packed weight is {q.out_features} x {q.in_features}, the "
-                             f"model's linear is {lin.out_features} x {lin.in_features}")
-        _set_submodule(model, name, q)
-        used.update(v for v in keys.values() if v in tensors)
-    return _load_rest(model, tensors, used, device)
 
 
 def _load_rest(model: torch.nn.Module, tensors: Dict[str, torch.Tensor], used, device):

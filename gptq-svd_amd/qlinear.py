@@ -49,6 +49,13 @@ Mixture of Experts (A19): ``QuantExperts`` replaces a layer's experts module
 weight format.  Its forward sorts the token-expert assignments by expert on the
 device and runs two ``tg_qgemm_grouped`` calls (``qgemm_grouped``), with no host
 synchronisation and no atomics.
+
+Structure: ``QuantLinear`` and ``MXQuantLinear`` derive from ``_PackedLinear``,
+which owns the bias / correction / rotation buffers, ``dequantize`` and the
+forward around the packed GEMM; a subclass adds its weight buffers, its shape
+checks, the decoded weight (``_dense``) and its ``tg_qgemm*`` call (``_gemm``).
+``_rows`` is the one place that turns an input into rows with a stride.
+``QuantExperts`` stands alone.
 """
 from __future__ import annotations
 
@@ -65,6 +72,17 @@ __all__ = ["QuantLinear", "dequantize_packed", "MXQuantLinear", "dequantize_pack
            "qgemm_grouped", "INT_ACT_FORMATS", "quantize_act_i8", "dequantize_act_i8"]
 
 _BITS = (2, 3, 4, 8)
+
+
+def _rows(x: torch.Tensor, n: int):
+    """``(x2, T, ldx)``: x as T rows of width n with unit column stride, a view
+    wherever the kernels' row stride ``ldx >= n`` can describe it and a copy
+    otherwise."""
+    x2 = x.reshape(-1, n)
+    T = x2.shape[0]
+    if T > 0 and (x2.stride(1) != 1 or (T > 1 and x2.stride(0) < n)):
+        x2 = x2.contiguous()
+    return x2, T, x2.stride(0) if T > 1 else n
 
 
 def _shapes(qweight: torch.Tensor, qzeros: torch.Tensor, scales: torch.Tensor, w_bits: int,
@@ -146,13 +164,9 @@ def hadamard(x: torch.Tensor, block: int, sign_bits: Optional[torch.Tensor],
             raise ValueError(f"sign_bits must be int32 of {n // 32} words, got {sign_bits.dtype} "
                              f"{tuple(sign_bits.shape)}")
         sign_bits = sign_bits.contiguous()
-    x2 = x.reshape(-1, n)
-    T = x2.shape[0]
+    x2, T, ldx = _rows(x, n)
     y = torch.empty((T, n), dtype=dtype, device=x.device)
     if T > 0:
-        if x2.stride(1) != 1 or (T > 1 and x2.stride(0) < n):
-            x2 = x2.contiguous()
-        ldx = x2.stride(0) if T > 1 else n
         with torch.cuda.device(x.device):
             call("tg_hadamard", stream(), ptr(x2), DTYPES[x.dtype], T, n, ldx, block,
                  ptr(sign_bits), int(bool(inverse)), ptr(y), DTYPES[dtype], n)
@@ -167,18 +181,6 @@ def _rotate_rows(x2: torch.Tensor, T: int, n: int, ldx: int, block: int,
         call("tg_hadamard", stream(), ptr(x2), DTYPES[x2.dtype], T, n, ldx, block, ptr(sign_bits),
              0, ptr(xr), DTYPES[x2.dtype], n)
     return xr
-
-
-def _register_rotation(mod: nn.Module, block: int, device) -> None:
-    """``rotate_block`` and the buffer ``had_sign`` (int32, in/32 words) for
-    block > 0; the attribute is None otherwise, like an absent bias."""
-    mod.rotate_block = int(block)
-    if mod.rotate_block:
-        _check_block(block, mod.in_features)
-        mod.register_buffer("had_sign", torch.zeros(mod.in_features // 32, dtype=torch.int32,
-                                                    device=device))
-    else:
-        mod.had_sign = None
 
 
 def _check_rotation(rotation, n: int):
@@ -209,22 +211,6 @@ def _check_lowrank(lowrank, m: int, n: int):
     if A.dtype not in _LR_DTYPES or B.dtype not in _LR_DTYPES:
         raise ValueError("lowrank factors must be float16, bfloat16 or float32")
     return A, B
-
-
-def _register_lowrank(mod: nn.Module, rank: int, dtype: torch.dtype, device) -> None:
-    """Buffers ``lr_a`` (out, r), ``lr_b`` (r, in) for rank > 0; the attributes
-    are None otherwise, like an absent bias."""
-    if rank:
-        if not 1 <= rank <= 128:
-            raise ValueError(f"lowrank must be in [0, 128], got {rank}")
-        if dtype not in _LR_DTYPES:
-            raise ValueError("lowrank_dtype must be float16, bfloat16 or float32")
-        mod.register_buffer("lr_a", torch.zeros((mod.out_features, rank), dtype=dtype,
-                                                device=device))
-        mod.register_buffer("lr_b", torch.zeros((rank, mod.in_features), dtype=dtype,
-                                                device=device))
-    else:
-        mod.lr_a = mod.lr_b = None
 
 
 def _lowrank_finish(x2: torch.Tensor, T: int, ldx: int, y32: torch.Tensor, lr_a: torch.Tensor,
@@ -269,11 +255,12 @@ def add_lowrank(W: torch.Tensor, A: torch.Tensor, B: torch.Tensor,
     return out
 
 
-def _check_int_act_format(act_format) -> None:
-    if act_format is not None and (not isinstance(act_format, str)
-                                   or act_format not in INT_ACT_FORMATS):
-        raise ValueError(f"act_format must be None or one of {sorted(INT_ACT_FORMATS)} for an "
-                         f"integer checkpoint, got {act_format!r}")
+def _check_act_format(act_format, allowed, where: str = "") -> None:
+    """None or a key of `allowed`; `where` names the kind of checkpoint that
+    takes only these."""
+    if act_format is not None and (not isinstance(act_format, str) or act_format not in allowed):
+        raise ValueError(f"act_format must be None or one of {sorted(allowed)}{where}, got "
+                         f"{act_format!r}")
 
 
 def quantize_act_i8(x: torch.Tensor):
@@ -286,14 +273,10 @@ def quantize_act_i8(x: torch.Tensor):
     n = x.shape[-1]
     if n == 0 or n % 32:
         raise ValueError(f"quantize_act_i8 needs a last dim that is a multiple of 32, got {n}")
-    x2 = x.reshape(-1, n)
-    T = x2.shape[0]
+    x2, T, ldx = _rows(x, n)
     xq = torch.empty((T, n), dtype=torch.int8, device=x.device)
     xs = torch.empty((T,), dtype=torch.float32, device=x.device)
     if T > 0:
-        if x2.stride(1) != 1 or (T > 1 and x2.stride(0) < n):
-            x2 = x2.contiguous()
-        ldx = x2.stride(0) if T > 1 else n
         with torch.cuda.device(x.device):
             call("tg_quant_act_i8", stream(), ptr(x2), DTYPES[x.dtype], T, ldx, n, 32, ptr(xq), n,
                  ptr(xs), None)
@@ -306,7 +289,117 @@ def dequantize_act_i8(xq: torch.Tensor, xs: torch.Tensor,
     return (xq.to(torch.float32) * xs.unsqueeze(-1)).to(dtype)
 
 
-class QuantLinear(nn.Module):
+class _PackedLinear(nn.Module):
+    """What ``QuantLinear`` and ``MXQuantLinear`` share: the optional buffers
+    (bias, low-rank correction, rotation) and everything around the one packed
+    GEMM of a forward.  A subclass registers its weight buffers, then calls
+    ``_register_extras``, and supplies ``_dense`` (the decoded weight) and
+    ``_gemm`` (its ``tg_qgemm*`` call)."""
+
+    def _register_extras(self, bias: bool, bias_dtype: torch.dtype, lowrank: int,
+                         lowrank_dtype: torch.dtype, rotate_block: int, device) -> None:
+        """Buffers ``bias`` (out,), ``lr_a`` (out, r) and ``lr_b`` (r, in), and
+        ``had_sign`` (int32, in/32 words) with ``rotate_block``; whatever is absent
+        is a None attribute."""
+        n, m = self.in_features, self.out_features
+        if bias:
+            self.register_buffer("bias", torch.zeros(m, dtype=bias_dtype, device=device))
+        else:
+            self.bias = None
+        if lowrank:
+            if not 1 <= lowrank <= 128:
+                raise ValueError(f"lowrank must be in [0, 128], got {lowrank}")
+            if lowrank_dtype not in _LR_DTYPES:
+                raise ValueError("lowrank_dtype must be float16, bfloat16 or float32")
+            self.register_buffer("lr_a", torch.zeros((m, lowrank), dtype=lowrank_dtype,
+                                                     device=device))
+            self.register_buffer("lr_b", torch.zeros((lowrank, n), dtype=lowrank_dtype,
+                                                     device=device))
+        else:
+            self.lr_a = self.lr_b = None
+        self.rotate_block = int(rotate_block)
+        if self.rotate_block:
+            _check_block(rotate_block, n)
+            self.register_buffer("had_sign", torch.zeros(n // 32, dtype=torch.int32, device=device))
+        else:
+            self.had_sign = None
+
+    @staticmethod
+    def _extras_args(m: int, n: int, bias, lowrank, rotation) -> dict:
+        """The constructor's keywords for the ``bias=``, ``lowrank=`` and
+        ``rotation=`` of a ``from_packed``, the last two checked against (m, n)."""
+        kw = dict(lowrank=0, lowrank_dtype=torch.float16, rotate_block=0)
+        if lowrank is not None:
+            A, _ = _check_lowrank(lowrank, m, n)
+            kw.update(lowrank=A.shape[1], lowrank_dtype=A.dtype)
+        if rotation is not None:
+            kw.update(rotate_block=_check_rotation(rotation, n)[0])
+        return dict(kw, bias=bias is not None,
+                    bias_dtype=bias.dtype if bias is not None else torch.float16)
+
+    def _fill(self, weights: dict, bias, lowrank, rotation):
+        """Copy a ``from_packed``'s tensors into the buffers; returns self."""
+        for name, t in weights.items():
+            getattr(self, name).copy_(t)
+        if bias is not None:
+            self.bias.copy_(bias.detach())
+        if lowrank is not None:
+            self.lr_a.copy_(lowrank[0].detach())
+            self.lr_b.copy_(lowrank[1].detach())
+        if rotation is not None:
+            self.had_sign.copy_(rotation[1])
+        return self
+
+    def _extras_repr(self) -> str:
+        lr = f", lowrank={self.lr_a.shape[1]}" if self.lr_a is not None else ""
+        return lr + (f", rotate_block={self.rotate_block}" if self.rotate_block else "")
+
+    def dequantize(self, dtype: torch.dtype = torch.float16, effective: bool = False,
+                   rotated: bool = True) -> torch.Tensor:
+        """The dense (out, in) weight; ``effective=True`` adds the low-rank
+        correction, W^ + lr_a lr_b (``add_lowrank``), when the layer has one.
+        A rotated layer stores the weight of the rotated basis, and that is what
+        ``rotated=True`` returns; ``rotated=False`` returns R^-1 of it (computed
+        from the fp32 matrix, rounded once to `dtype`), the matrix for which
+        ``x @ W.T`` approximates the forward."""
+        back = self.rotate_block and not rotated
+        dt = torch.float32 if back else dtype
+        if effective and self.lr_a is not None:
+            W = add_lowrank(self._dense(torch.float32), self.lr_a, self.lr_b, dt)
+        else:
+            W = self._dense(dt)
+        return hadamard(W, self.rotate_block, self.had_sign, inverse=True, dtype=dtype) \
+            if back else W
+
+    @torch.no_grad()
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if not (x.is_cuda and self.qweight.is_cuda):    # the names are built off the hot path
+            require_cuda(x, f"{type(self).__name__} input")
+            require_cuda(self.qweight, f"{type(self).__name__}.qweight")
+        if x.dtype not in (torch.float16, torch.bfloat16):
+            raise RuntimeError(f"{type(self).__name__} takes float16 or bfloat16 activations, got "
+                               f"{x.dtype} (there is no fp32 kernel and no fallback)")
+        if x.shape[-1] != self.in_features:
+            raise RuntimeError(f"{type(self).__name__}: last dim {x.shape[-1]} != in_features "
+                               f"{self.in_features}")
+        n, m = self.in_features, self.out_features
+        x2, T, ldx = _rows(x, n)
+        y = torch.empty((T, m), dtype=x.dtype, device=x.device)
+        if T > 0:
+            if self.rotate_block:
+                x2, ldx = _rotate_rows(x2, T, n, ldx, self.rotate_block, self.had_sign), n
+            lr = self.lr_a is not None
+            # with a correction the GEMM leaves its fp32 sums; tg_lr_finish adds the bias.
+            # Z = x lr_b^T always comes from the 16-bit x, under act_format too.
+            out = torch.empty((T, m), dtype=torch.float32, device=x.device) if lr else y
+            with torch.cuda.device(x.device):
+                self._gemm(x2, T, ldx, None if lr else self.bias, out)
+                if lr:
+                    _lowrank_finish(x2, T, ldx, out, self.lr_a, self.lr_b, self.bias, y)
+        return y.reshape(*x.shape[:-1], m)
+
+
+class QuantLinear(_PackedLinear):
     """A linear layer whose weight stays packed.  The buffer names are the
     checkpoint's keys, so ``load_state_dict`` fills it.  ``module.to(dtype)``
     converts floating buffers like any module: fp32 ``scales`` become 16-bit
@@ -322,7 +415,7 @@ class QuantLinear(nn.Module):
                  lowrank_dtype: torch.dtype = torch.float16, rotate_block: int = 0,
                  act_format=None):
         super().__init__()
-        _check_int_act_format(act_format)
+        _check_act_format(act_format, INT_ACT_FORMATS, " for an integer checkpoint")
         self.act_format = act_format
         if w_bits not in _BITS:
             raise ValueError(f"w_bits must be one of {_BITS}, got {w_bits}")
@@ -343,12 +436,7 @@ class QuantLinear(nn.Module):
                                                    device=device))
         self.register_buffer("g_idx", (torch.arange(in_features, dtype=torch.int32,
                                                     device=device) // g).to(torch.int32))
-        if bias:
-            self.register_buffer("bias", torch.zeros(out_features, dtype=bias_dtype, device=device))
-        else:
-            self.bias = None
-        _register_lowrank(self, int(lowrank), lowrank_dtype, device)
-        _register_rotation(self, rotate_block, device)
+        self._register_extras(bias, bias_dtype, int(lowrank), lowrank_dtype, rotate_block, device)
 
     @classmethod
     def from_packed(cls, qweight: torch.Tensor, qzeros: torch.Tensor, scales: torch.Tensor,
@@ -361,110 +449,47 @@ class QuantLinear(nn.Module):
         ``rotation=(block, sign_bits)``: the packed weight is that of the rotated
         basis and the forward rotates x first.  ``act_format``: None or "int8"."""
         m, n, g = _shapes(qweight, qzeros, scales, w_bits, group_size)
-        if lowrank is not None:
-            lowrank = _check_lowrank(lowrank, m, n)
-        if rotation is not None:
-            rotation = _check_rotation(rotation, n)
+        extras = cls._extras_args(m, n, bias, lowrank, rotation)
         if g_idx is not None:
             triv = torch.arange(n, dtype=torch.int64) // g
             if tuple(g_idx.shape) != (n,) or not torch.equal(g_idx.cpu().to(torch.int64), triv):
                 raise ValueError("g_idx is not the static arange(in_features) // group_size map "
                                  "(act-order checkpoints are not supported)")
         dev = device if device is not None else qweight.device
-        q = cls(n, m, w_bits, group_size, bias=bias is not None, scale_dtype=scales.dtype,
-                bias_dtype=bias.dtype if bias is not None else torch.float16, device=dev,
-                lowrank=lowrank[0].shape[1] if lowrank is not None else 0,
-                lowrank_dtype=lowrank[0].dtype if lowrank is not None else torch.float16,
-                rotate_block=rotation[0] if rotation is not None else 0, act_format=act_format)
-        q.qweight.copy_(qweight)
-        q.qzeros.copy_(qzeros)
-        q.scales.copy_(scales)
-        if bias is not None:
-            q.bias.copy_(bias.detach())
-        if lowrank is not None:
-            q.lr_a.copy_(lowrank[0].detach())
-            q.lr_b.copy_(lowrank[1].detach())
-        if rotation is not None:
-            q.had_sign.copy_(rotation[1])
-        return q
+        q = cls(n, m, w_bits, group_size, scale_dtype=scales.dtype, device=dev,
+                act_format=act_format, **extras)
+        return q._fill(dict(qweight=qweight, qzeros=qzeros, scales=scales), bias, lowrank, rotation)
 
     def extra_repr(self) -> str:
-        lr = f", lowrank={self.lr_a.shape[1]}" if self.lr_a is not None else ""
-        if self.rotate_block:
-            lr += f", rotate_block={self.rotate_block}"
-        if self.act_format is not None:
-            lr += f", act_format={self.act_format}"
+        act = f", act_format={self.act_format}" if self.act_format is not None else ""
         return (f"in_features={self.in_features}, out_features={self.out_features}, "
                 f"bits={self.w_bits}, group_size={self.group_size}, "
-                f"bias={self.bias is not None}{lr}")
+                f"bias={self.bias is not None}{self._extras_repr()}{act}")
 
-    def dequantize(self, dtype: torch.dtype = torch.float16, effective: bool = False,
-                   rotated: bool = True) -> torch.Tensor:
-        """The dense (out, in) weight; ``effective=True`` adds the low-rank
-        correction, W^ + lr_a lr_b (``add_lowrank``), when the layer has one.
-        A rotated layer stores the weight of the rotated basis, and that is what
-        ``rotated=True`` returns; ``rotated=False`` returns R^-1 of it (computed
-        from the fp32 matrix, rounded once to `dtype`), the matrix for which
-        ``x @ W.T`` approximates the forward."""
-        back = self.rotate_block and not rotated
-        dt = torch.float32 if back else dtype
-        if effective and self.lr_a is not None:
-            W = dequantize_packed(self.qweight, self.qzeros, self.scales, self.w_bits,
-                                  self.group_size, torch.float32)
-            W = add_lowrank(W, self.lr_a, self.lr_b, dt)
-        else:
-            W = dequantize_packed(self.qweight, self.qzeros, self.scales, self.w_bits,
-                                  self.group_size, dt)
-        return hadamard(W, self.rotate_block, self.had_sign, inverse=True, dtype=dtype) \
-            if back else W
+    def _dense(self, dtype: torch.dtype) -> torch.Tensor:
+        return dequantize_packed(self.qweight, self.qzeros, self.scales, self.w_bits,
+                                 self.group_size, dtype)
 
-    @torch.no_grad()
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        require_cuda(x, "QuantLinear input")
-        require_cuda(self.qweight, "QuantLinear.qweight")
-        if x.dtype not in (torch.float16, torch.bfloat16):
-            raise RuntimeError(f"QuantLinear takes float16 or bfloat16 activations, got {x.dtype} "
-                               "(there is no fp32 kernel and no fallback)")
-        if x.shape[-1] != self.in_features:
-            raise RuntimeError(f"QuantLinear: last dim {x.shape[-1]} != in_features "
-                               f"{self.in_features}")
+    def _gemm(self, x2: torch.Tensor, T: int, ldx: int, bias: Optional[torch.Tensor],
+              out: torch.Tensor) -> None:
         n, m = self.in_features, self.out_features
-        x2 = x.reshape(-1, n)
-        T = x2.shape[0]
-        y = torch.empty((T, m), dtype=x.dtype, device=x.device)
-        if T > 0:
-            if x2.stride(1) != 1 or (T > 1 and x2.stride(0) < n):
-                x2 = x2.contiguous()
-            ldx = x2.stride(0) if T > 1 else n
-            if self.rotate_block:
-                x2, ldx = _rotate_rows(x2, T, n, ldx, self.rotate_block, self.had_sign), n
-            bias = self.bias
-            lr = self.lr_a is not None
-            # with a correction the GEMM leaves its fp32 sums; tg_lr_finish adds the bias.
-            # Z = x lr_b^T always comes from the 16-bit x, under act_format too.
-            out = torch.empty((T, m), dtype=torch.float32, device=x.device) if lr else y
-            gb = None if lr else bias
-            with torch.cuda.device(x.device):
-                if self.act_format is not None:
-                    nbytes = lib.tg_qgemm_act_workspace_size(T, m, n, self.group_size)
-                    ws = workspace(nbytes, x.device)
-                    call("tg_qgemm_act", stream(), ptr(x2), DTYPES[x.dtype], T, ldx,
-                         ptr(self.qweight), ptr(self.qzeros), ptr(self.scales),
-                         DTYPES[self.scales.dtype], m, n, self.group_size, self.w_bits,
-                         INT_ACT_FORMATS[self.act_format], ptr(gb),
-                         DTYPES[gb.dtype] if gb is not None else 0, ptr(out), DTYPES[out.dtype], m,
-                         ptr(ws), nbytes)
-                else:
-                    nbytes = lib.tg_qgemm_workspace_size(T, m, n)
-                    ws = workspace(nbytes, x.device)
-                    call("tg_qgemm", stream(), ptr(x2), DTYPES[x.dtype], T, ldx,
-                         ptr(self.qweight), ptr(self.qzeros), ptr(self.scales),
-                         DTYPES[self.scales.dtype], m, n, self.group_size, self.w_bits, ptr(gb),
-                         DTYPES[gb.dtype] if gb is not None else 0, ptr(out), DTYPES[out.dtype], m,
-                         ptr(ws), nbytes)
-                if lr:
-                    _lowrank_finish(x2, T, ldx, out, self.lr_a, self.lr_b, bias, y)
-        return y.reshape(*x.shape[:-1], m)
+        if self.act_format is not None:
+            nbytes = lib.tg_qgemm_act_workspace_size(T, m, n, self.group_size)
+            ws = workspace(nbytes, x2.device)
+            call("tg_qgemm_act", stream(), ptr(x2), DTYPES[x2.dtype], T, ldx,
+                 ptr(self.qweight), ptr(self.qzeros), ptr(self.scales),
+                 DTYPES[self.scales.dtype], m, n, self.group_size, self.w_bits,
+                 INT_ACT_FORMATS[self.act_format], ptr(bias),
+                 DTYPES[bias.dtype] if bias is not None else 0, ptr(out), DTYPES[out.dtype], m,
+                 ptr(ws), nbytes)
+        else:
+            nbytes = lib.tg_qgemm_workspace_size(T, m, n)
+            ws = workspace(nbytes, x2.device)
+            call("tg_qgemm", stream(), ptr(x2), DTYPES[x2.dtype], T, ldx,
+                 ptr(self.qweight), ptr(self.qzeros), ptr(self.scales),
+                 DTYPES[self.scales.dtype], m, n, self.group_size, self.w_bits, ptr(bias),
+                 DTYPES[bias.dtype] if bias is not None else 0, ptr(out), DTYPES[out.dtype], m,
+                 ptr(ws), nbytes)
 
 
 # ---------------------------------------------------------------------------
@@ -508,13 +533,6 @@ def dequantize_packed_mx(qweight: torch.Tensor, scales: torch.Tensor,
     return out
 
 
-def _check_act_format(act_format) -> None:
-    if act_format is not None and (not isinstance(act_format, str)
-                                   or act_format not in ACT_FORMATS):
-        raise ValueError(f"act_format must be None or one of {sorted(ACT_FORMATS)}, got "
-                         f"{act_format!r}")
-
-
 def quantize_act_mx(x: torch.Tensor):
     """MXFP8 image of fp16 / bf16 activations (..., n), n % 32 == 0:
     ``(xq uint8 (..., n), xs uint8 (..., n/32))``, e4m3fn bytes (OCP) and the
@@ -525,14 +543,10 @@ def quantize_act_mx(x: torch.Tensor):
     n = x.shape[-1]
     if n == 0 or n % 32:
         raise ValueError(f"quantize_act_mx needs a last dim that is a multiple of 32, got {n}")
-    x2 = x.reshape(-1, n)
-    T = x2.shape[0]
+    x2, T, ldx = _rows(x, n)
     xq = torch.empty((T, n), dtype=torch.uint8, device=x.device)
     xs = torch.empty((T, n // 32), dtype=torch.uint8, device=x.device)
     if T > 0:
-        if x2.stride(1) != 1 or (T > 1 and x2.stride(0) < n):
-            x2 = x2.contiguous()
-        ldx = x2.stride(0) if T > 1 else n
         with torch.cuda.device(x.device):
             call("tg_quant_act_mx", stream(), ptr(x2), DTYPES[x.dtype], T, ldx, n,
                  ACT_FORMATS["mxfp8"], ptr(xq), n, ptr(xs))
@@ -550,7 +564,7 @@ def dequantize_act_mx(xq: torch.Tensor, xs: torch.Tensor,
     return (v * s.repeat_interleave(32, dim=-1)).to(dtype)
 
 
-class MXQuantLinear(nn.Module):
+class MXQuantLinear(_PackedLinear):
     """A linear layer whose weight stays packed as MXFP4: buffers ``qweight``
     int32 (in/8, out) and ``scales`` uint8 (in/32, out), the checkpoint's keys.
     ``act_format=None``: weights only, activations are fp16 / bf16 and the
@@ -566,7 +580,7 @@ class MXQuantLinear(nn.Module):
                  lowrank: int = 0, lowrank_dtype: torch.dtype = torch.float16,
                  rotate_block: int = 0):
         super().__init__()
-        _check_act_format(act_format)
+        _check_act_format(act_format, ACT_FORMATS)
         self.act_format = act_format
         if in_features % 32 or (out_features * 4) % 32:
             raise ValueError(f"MXQuantLinear needs in_features % 32 == 0 and out_features % 8 == 0 "
@@ -577,12 +591,7 @@ class MXQuantLinear(nn.Module):
         # byte 127 = scale 1
         self.register_buffer("scales", torch.full((in_features // 32, out_features), 127,
                                                   dtype=torch.uint8, device=device))
-        if bias:
-            self.register_buffer("bias", torch.zeros(out_features, dtype=bias_dtype, device=device))
-        else:
-            self.bias = None
-        _register_lowrank(self, int(lowrank), lowrank_dtype, device)
-        _register_rotation(self, rotate_block, device)
+        self._register_extras(bias, bias_dtype, int(lowrank), lowrank_dtype, rotate_block, device)
 
     @classmethod
     def from_packed(cls, qweight: torch.Tensor, scales: torch.Tensor,
@@ -593,101 +602,37 @@ class MXQuantLinear(nn.Module):
         ``rotation=(block, sign_bits)``: the packed weight is that of the rotated
         basis and the forward rotates x first."""
         m, n = _shapes_mx(qweight, scales)
-        if lowrank is not None:
-            lowrank = _check_lowrank(lowrank, m, n)
-        if rotation is not None:
-            rotation = _check_rotation(rotation, n)
+        extras = cls._extras_args(m, n, bias, lowrank, rotation)
         dev = device if device is not None else qweight.device
-        q = cls(n, m, bias=bias is not None,
-                bias_dtype=bias.dtype if bias is not None else torch.float16, device=dev,
-                act_format=act_format,
-                lowrank=lowrank[0].shape[1] if lowrank is not None else 0,
-                lowrank_dtype=lowrank[0].dtype if lowrank is not None else torch.float16,
-                rotate_block=rotation[0] if rotation is not None else 0)
-        q.qweight.copy_(qweight)
-        q.scales.copy_(scales)
-        if bias is not None:
-            q.bias.copy_(bias.detach())
-        if lowrank is not None:
-            q.lr_a.copy_(lowrank[0].detach())
-            q.lr_b.copy_(lowrank[1].detach())
-        if rotation is not None:
-            q.had_sign.copy_(rotation[1])
-        return q
+        q = cls(n, m, device=dev, act_format=act_format, **extras)
+        return q._fill(dict(qweight=qweight, scales=scales), bias, lowrank, rotation)
 
     def extra_repr(self) -> str:
-        lr = f", lowrank={self.lr_a.shape[1]}" if self.lr_a is not None else ""
-        if self.rotate_block:
-            lr += f", rotate_block={self.rotate_block}"
         return (f"in_features={self.in_features}, out_features={self.out_features}, "
-                f"format=mxfp4, bias={self.bias is not None}, act_format={self.act_format}{lr}")
+                f"format=mxfp4, bias={self.bias is not None}, act_format={self.act_format}"
+                f"{self._extras_repr()}")
 
-    def dequantize(self, dtype: torch.dtype = torch.float16, effective: bool = False,
-                   rotated: bool = True) -> torch.Tensor:
-        """The dense (out, in) weight; ``effective=True`` adds the low-rank
-        correction, W^ + lr_a lr_b (``add_lowrank``), when the layer has one.
-        A rotated layer stores the weight of the rotated basis, and that is what
-        ``rotated=True`` returns; ``rotated=False`` returns R^-1 of it (computed
-        from the fp32 matrix, rounded once to `dtype`), the matrix for which
-        ``x @ W.T`` approximates the forward."""
-        back = self.rotate_block and not rotated
-        dt = torch.float32 if back else dtype
-        if effective and self.lr_a is not None:
-            W = add_lowrank(dequantize_packed_mx(self.qweight, self.scales, torch.float32),
-                            self.lr_a, self.lr_b, dt)
-        else:
-            W = dequantize_packed_mx(self.qweight, self.scales, dt)
-        return hadamard(W, self.rotate_block, self.had_sign, inverse=True, dtype=dtype) \
-            if back else W
+    def _dense(self, dtype: torch.dtype) -> torch.Tensor:
+        return dequantize_packed_mx(self.qweight, self.scales, dtype)
 
-    @torch.no_grad()
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        require_cuda(x, "MXQuantLinear input")
-        require_cuda(self.qweight, "MXQuantLinear.qweight")
-        if x.dtype not in (torch.float16, torch.bfloat16):
-            raise RuntimeError(f"MXQuantLinear takes float16 or bfloat16 activations, got "
-                               f"{x.dtype} (there is no fp32 kernel and no fallback)")
-        if x.shape[-1] != self.in_features:
-            raise RuntimeError(f"MXQuantLinear: last dim {x.shape[-1]} != in_features "
-                               f"{self.in_features}")
+    def _gemm(self, x2: torch.Tensor, T: int, ldx: int, bias: Optional[torch.Tensor],
+              out: torch.Tensor) -> None:
         n, m = self.in_features, self.out_features
-        x2 = x.reshape(-1, n)
-        T = x2.shape[0]
-        y = torch.empty((T, m), dtype=x.dtype, device=x.device)
-        if T > 0:
-            if x2.stride(1) != 1 or (T > 1 and x2.stride(0) < n):
-                x2 = x2.contiguous()
-            ldx = x2.stride(0) if T > 1 else n
-            if self.rotate_block:
-                x2, ldx = _rotate_rows(x2, T, n, ldx, self.rotate_block, self.had_sign), n
-            bias = self.bias
-            lr = self.lr_a is not None
-            # with a correction the GEMM leaves its fp32 sums; tg_lr_finish adds the bias.
-            # Z = x lr_b^T always comes from the 16-bit x, under act_format too.
-            out = torch.empty((T, m), dtype=torch.float32, device=x.device) if lr else y
-            gb = None if lr else bias
-            if self.act_format is not None:
-                with torch.cuda.device(x.device):
-                    nbytes = lib.tg_qgemm_mx_act_workspace_size(T, m, n)
-                    ws = workspace(nbytes, x.device)
-                    call("tg_qgemm_mx_act", stream(), ptr(x2), DTYPES[x.dtype], T, ldx,
-                         ptr(self.qweight), ptr(self.scales), TG_FMT_MXFP4,
-                         ACT_FORMATS[self.act_format], m, n, ptr(gb),
-                         DTYPES[gb.dtype] if gb is not None else 0, ptr(out), DTYPES[out.dtype],
-                         m, ptr(ws), nbytes)
-                    if lr:
-                        _lowrank_finish(x2, T, ldx, out, self.lr_a, self.lr_b, bias, y)
-                return y.reshape(*x.shape[:-1], m)
-            with torch.cuda.device(x.device):
-                nbytes = lib.tg_qgemm_workspace_size(T, m, n)
-                ws = workspace(nbytes, x.device)
-                call("tg_qgemm_mx", stream(), ptr(x2), DTYPES[x.dtype], T, ldx, ptr(self.qweight),
-                     ptr(self.scales), TG_FMT_MXFP4, m, n, ptr(gb),
-                     DTYPES[gb.dtype] if gb is not None else 0, ptr(out), DTYPES[out.dtype], m,
-                     ptr(ws), nbytes)
-                if lr:
-                    _lowrank_finish(x2, T, ldx, out, self.lr_a, self.lr_b, bias, y)
-        return y.reshape(*x.shape[:-1], m)
+        if self.act_format is not None:
+            nbytes = lib.tg_qgemm_mx_act_workspace_size(T, m, n)
+            ws = workspace(nbytes, x2.device)
+            call("tg_qgemm_mx_act", stream(), ptr(x2), DTYPES[x2.dtype], T, ldx,
+                 ptr(self.qweight), ptr(self.scales), TG_FMT_MXFP4,
+                 ACT_FORMATS[self.act_format], m, n, ptr(bias),
+                 DTYPES[bias.dtype] if bias is not None else 0, ptr(out), DTYPES[out.dtype],
+                 m, ptr(ws), nbytes)
+        else:
+            nbytes = lib.tg_qgemm_workspace_size(T, m, n)
+            ws = workspace(nbytes, x2.device)
+            call("tg_qgemm_mx", stream(), ptr(x2), DTYPES[x2.dtype], T, ldx, ptr(self.qweight),
+                 ptr(self.scales), TG_FMT_MXFP4, m, n, ptr(bias),
+                 DTYPES[bias.dtype] if bias is not None else 0, ptr(out), DTYPES[out.dtype], m,
+                 ptr(ws), nbytes)
 
 
 # ---------------------------------------------------------------------------
@@ -725,9 +670,7 @@ def qgemm_grouped(x: torch.Tensor, rows: Optional[torch.Tensor], offsets: torch.
     y = torch.empty((R, m), dtype=dtype, device=x.device)
     if R == 0:
         return y
-    if x.stride(1) != 1 or (T > 1 and x.stride(0) < n):
-        x = x.contiguous()
-    ldx = x.stride(0) if T > 1 else n
+    x, T, ldx = _rows(x, n)
     with torch.cuda.device(x.device):
         nbytes = lib.tg_qgemm_grouped_workspace_size(R, E, m, n)
         ws = workspace(nbytes, x.device)

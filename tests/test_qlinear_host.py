@@ -150,3 +150,52 @@ def test_load_quantized_rejects_act_order(tmp_path, oracle_mod):
     json.dump(qc, open(cfg, "w"))
     with pytest.raises(ValueError, match="desc_act"):
         load_quantized(fresh(), str(tmp_path))
+
+
+# (key, dtype, shape) of each buffer, in the order state_dict() lists them: the
+# format's own weight buffers, then bias, lr_a / lr_b, had_sign when present
+I32, F16T, U8 = torch.int32, torch.float16, torch.uint8
+LAYOUT = {
+    "QuantLinear": [("qweight", I32, (8, 8)), ("qzeros", I32, (2, 1)), ("scales", F16T, (2, 8)),
+                    ("g_idx", I32, (64,))],
+    "MXQuantLinear": [("qweight", I32, (8, 8)), ("scales", U8, (2, 8))],
+}
+BIAS = [("bias", F16T, (8,))]
+LOWRANK = [("lr_a", F16T, (8, 4)), ("lr_b", F16T, (4, 64))]
+ROTATION = [("had_sign", I32, (2,))]
+
+
+def packed_linear(cls, **kw):
+    from gptq_svd_amd import qlinear
+    if cls == "QuantLinear":
+        return qlinear.QuantLinear(64, 8, 4, 32, **kw)
+    return qlinear.MXQuantLinear(64, 8, **kw)
+
+
+@pytest.mark.parametrize("rotate_block", [0, 32])
+@pytest.mark.parametrize("lowrank", [0, 4])
+@pytest.mark.parametrize("bias", [False, True])
+@pytest.mark.parametrize("cls", ["QuantLinear", "MXQuantLinear"])
+def test_state_dict_layout_is_pinned(cls, bias, lowrank, rotate_block):
+    """Buffer names, dtypes, shapes and order are the checkpoint's keys: they
+    must not move.  An absent bias, correction or rotation is a None attribute."""
+    q = packed_linear(cls, bias=bias, lowrank=lowrank, rotate_block=rotate_block)
+    want = LAYOUT[cls] + (BIAS if bias else []) + (LOWRANK if lowrank else []) \
+        + (ROTATION if rotate_block else [])
+    assert [(k, v.dtype, tuple(v.shape)) for k, v in q.state_dict().items()] == want
+    assert (q.bias is None) == (not bias)
+    assert (q.lr_a is None) == (not lowrank) and (q.lr_b is None) == (not lowrank)
+    assert (q.had_sign is None) == (not rotate_block) and q.rotate_block == rotate_block
+
+
+def test_repr_is_pinned():
+    q = packed_linear("QuantLinear", bias=True, lowrank=4, rotate_block=32, act_format="int8")
+    assert repr(q) == ("QuantLinear(in_features=64, out_features=8, bits=4, group_size=32, "
+                       "bias=True, lowrank=4, rotate_block=32, act_format=int8)")
+    assert repr(packed_linear("QuantLinear")) == \
+        "QuantLinear(in_features=64, out_features=8, bits=4, group_size=32, bias=False)"
+    q = packed_linear("MXQuantLinear", bias=True, lowrank=4, rotate_block=32, act_format="mxfp8")
+    assert repr(q) == ("MXQuantLinear(in_features=64, out_features=8, format=mxfp4, bias=True, "
+                       "act_format=mxfp8, lowrank=4, rotate_block=32)")
+    assert repr(packed_linear("MXQuantLinear")) == \
+        "MXQuantLinear(in_features=64, out_features=8, format=mxfp4, bias=False, act_format=None)"
