@@ -261,7 +261,7 @@ def _set_submodule(model: torch.nn.Module, name: str, new: torch.nn.Module) -> N
 
 
 def load_quantized(model: torch.nn.Module, path: str, device=None,
-                   act_format=None) -> torch.nn.Module:
+                   act_format=None, act_order: bool = False) -> torch.nn.Module:
     """Load a checkpoint written by save_quantized into `model` (the dense
     architecture, any weights) and return it: every ``nn.Linear`` whose
     ``<name>.qweight`` is in the checkpoint becomes a ``qlinear.QuantLinear``
@@ -280,7 +280,14 @@ def load_quantized(model: torch.nn.Module, path: str, device=None,
     per-token INT8 activations on the i8 MFMA (``QuantLinear``), for integer
     (``gptq_v2``) checkpoints only.  A format with the other kind of checkpoint,
     an unknown format, and any format with a Mixture-of-Experts checkpoint are a
-    ``ValueError`` before any tensor is read."""
+    ``ValueError`` before any tensor is read.
+    ``act_order=True`` lifts the two refusals for integer checkpoints:
+    ``desc_act=true`` is accepted, and a linear whose ``g_idx`` is any map with
+    `group_size` columns in every group is sorted by group as it is loaded
+    (``QuantLinear.from_packed(..., act_order=True)``).  The sort is a kernel, so
+    such a layer is built on `device` when that is given and on the model's device
+    otherwise, and one of them must be a GPU.  MXFP4 and experts checkpoints have
+    no ``g_idx``; nothing changes for them."""
     from .qlinear import ACT_FORMATS, INT_ACT_FORMATS, MXQuantLinear, QuantLinear
     if act_format is not None:                   # before any tensor is read
         known = sorted(ACT_FORMATS) + sorted(INT_ACT_FORMATS)
@@ -317,7 +324,7 @@ def load_quantized(model: torch.nn.Module, path: str, device=None,
     else:
         if bits not in (2, 3, 4, 8):
             raise ValueError(f"quantize_config.json: bits={bits} is not one of 2, 3, 4, 8")
-        if qc.get("desc_act", False):
+        if qc.get("desc_act", False) and not act_order:
             raise ValueError("quantize_config.json: desc_act=true (act-order) checkpoints are not "
                              "supported")
         if not isinstance(qc.get("sym"), bool):
@@ -329,10 +336,12 @@ def load_quantized(model: torch.nn.Module, path: str, device=None,
         required = ("qzeros", "scales", "g_idx")
 
         def build(t, keys, bias, lowrank, rotation, dev):
+            if act_order and device is not None:
+                dev = device               # an act-order layer is sorted where it will run
             return QuantLinear.from_packed(t[keys["qweight"]], t[keys["qzeros"]], t[keys["scales"]],
                                            bits, group, bias=bias, g_idx=t[keys["g_idx"]],
                                            device=dev, lowrank=lowrank, rotation=rotation,
-                                           act_format=act_format)
+                                           act_format=act_format, act_order=act_order)
     used = set()
     _load_experts(model, tensors, qc, used)
     _load_linears(model, tensors, used, blocks, required, build)

@@ -8,9 +8,17 @@ split-K GEMV for up to 16 rows, an MFMA tile kernel above).  Both are HIP
 kernels; there is no CPU or eager fallback.
 
 Layout (export.py): ``qweight`` int32 (in*b/32, out), ``qzeros`` int32
-(G, out*b/32), ``scales`` fp16 or fp32 (G, out), ``g_idx`` int32 (in,) -- only
-the trivial map ``arange(in) // group`` (static groups, original column
-order).  w = (code_u - zero_u) * scale.
+(G, out*b/32), ``scales`` fp16 or fp32 (G, out), ``g_idx`` int32 (in,) -- by
+default only the trivial map ``arange(in) // group`` (static groups, original
+column order).  w = (code_u - zero_u) * scale.
+
+Act-order checkpoints (A21, opt-in with ``act_order=True``): ``g_idx[c]`` is the
+group of column c, any map that gives every group exactly ``group`` columns.
+The packed stream is sorted by group once at load (``tg_repack_gidx``) and the
+forward permutes the activation columns instead (``tg_qgemm_gidx``: fused into
+the GEMV's staging at decode, one ``tg_gather_cols`` launch in front of the
+tile kernel above), so the hot loops still fetch one zero and one scale per
+unit of 32 values; ``tg_dequant_gidx`` returns the original column order.
 
 MXFP4 checkpoints (``checkpoint_format: "mxfp4"``) hold ``qweight`` int32
 (in/8, out), the same 4-bit stream of E2M1 codes, and ``scales`` uint8
@@ -109,18 +117,69 @@ def _shapes(qweight: torch.Tensor, qzeros: torch.Tensor, scales: torch.Tensor, w
     return m, n, g
 
 
+def _gidx_plan(g_idx: torch.Tensor, n: int, g: int) -> Optional[torch.Tensor]:
+    """The load-time plan of an act-order layer: ``col_perm = argsort(g_idx,
+    stable)`` as a CPU int32 tensor (the columns of group 0 in ascending order,
+    then group 1, ...), or None for the trivial map, which is the static layer.
+    Every value of `g_idx` must lie in [0, n/g) and every group have g columns."""
+    if tuple(g_idx.shape) != (n,):
+        raise ValueError(f"g_idx must have shape ({n},), got {tuple(g_idx.shape)}")
+    gi = g_idx.detach().cpu().to(torch.int64)
+    if torch.equal(gi, torch.arange(n, dtype=torch.int64) // g):
+        return None
+    G = n // g
+    if int(gi.min()) < 0 or int(gi.max()) >= G:
+        raise ValueError(f"g_idx has values outside [0, {G}) (in_features {n}, group {g})")
+    if not bool((torch.bincount(gi, minlength=G) == g).all()):
+        raise ValueError(f"g_idx does not give every group exactly {g} columns")
+    return torch.argsort(gi, stable=True).to(torch.int32)
+
+
+def _repack_gidx(qweight: torch.Tensor, col_perm: torch.Tensor, w_bits: int) -> torch.Tensor:
+    """The stream sorted by group: position j holds the code of column
+    ``col_perm[j]`` (``tg_repack_gidx``); both tensors on one GPU."""
+    require_cuda(qweight, "act-order qweight")
+    qweight = qweight.contiguous()
+    nw, m = qweight.shape
+    out = torch.empty_like(qweight)
+    with torch.cuda.device(qweight.device):
+        call("tg_repack_gidx", stream(), ptr(qweight), ptr(col_perm), m, nw * 32 // w_bits, w_bits,
+             ptr(out))
+    return out
+
+
+def _dequant_gidx(qsorted: torch.Tensor, qzeros: torch.Tensor, scales: torch.Tensor,
+                  col_perm: torch.Tensor, m: int, n: int, g: int, w_bits: int,
+                  dtype: torch.dtype) -> torch.Tensor:
+    out = torch.empty((m, n), dtype=dtype, device=qsorted.device)
+    with torch.cuda.device(qsorted.device):
+        call("tg_dequant_gidx", stream(), ptr(qsorted), ptr(qzeros), ptr(scales),
+             DTYPES[scales.dtype], m, n, g, w_bits, ptr(out), DTYPES[dtype], n, ptr(col_perm))
+    return out
+
+
 def dequantize_packed(qweight: torch.Tensor, qzeros: torch.Tensor, scales: torch.Tensor,
-                      w_bits: int, group_size: int,
-                      dtype: torch.dtype = torch.float16) -> torch.Tensor:
+                      w_bits: int, group_size: int, dtype: torch.dtype = torch.float16,
+                      g_idx: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Dense weight (out, in) of `dtype` (fp16 / bf16 / fp32):
-    ``float(code_u - zero_u) * float(scale)`` rounded once to `dtype`."""
+    ``float(code_u - zero_u) * float(scale)`` rounded once to `dtype`.  With a
+    `g_idx` (the tensors in checkpoint layout) column c takes the zero and scale
+    of group ``g_idx[c]``: the stream is sorted by group (``tg_repack_gidx``) and
+    decoded back into the original column order (``tg_dequant_gidx``)."""
     m, n, g = _shapes(qweight, qzeros, scales, w_bits, group_size)
+    col_perm = None if g_idx is None else _gidx_plan(g_idx, n, g)
+    if col_perm is not None and n % 32:
+        raise ValueError(f"a non-trivial g_idx needs in_features % 32 == 0, got {n}")
     for t, what in ((qweight, "qweight"), (qzeros, "qzeros"), (scales, "scales")):
         require_cuda(t, what)
     if dtype not in (torch.float16, torch.bfloat16, torch.float32):
         raise ValueError(f"dtype must be float16, bfloat16 or float32, got {dtype}")
     dev = qweight.device
     qweight, qzeros, scales = qweight.contiguous(), qzeros.contiguous(), scales.contiguous()
+    if col_perm is not None:
+        col_perm = col_perm.to(dev)
+        return _dequant_gidx(_repack_gidx(qweight, col_perm, w_bits), qzeros, scales, col_perm,
+                             m, n, g, w_bits, dtype)
     out = torch.empty((m, n), dtype=dtype, device=dev)
     with torch.cuda.device(dev):
         call("tg_dequant_packed", stream(), ptr(qweight), ptr(qzeros), ptr(scales),
@@ -407,7 +466,13 @@ class QuantLinear(_PackedLinear):
     ``act_format=None``: weights only, the codes are decoded to x's dtype
     (``tg_qgemm``).  ``act_format="int8"``: x is quantised per token to int8 per
     call and both operands feed the i8 MFMA (``tg_qgemm_act``); a run-time choice
-    that the checkpoint does not record."""
+    that the checkpoint does not record.
+    An act-order layer (``from_packed(..., act_order=True)`` with a non-trivial
+    `g_idx`) holds the stream sorted by group in ``qweight``, the checkpoint's
+    map in ``g_idx`` and ``col_perm = argsort(g_idx)`` as a non-persistent
+    buffer (None for a static layer).  Its ``state_dict()`` therefore holds the
+    sorted stream beside the unsorted map: it is not a checkpoint, and loading it
+    anywhere, into another ``QuantLinear`` included, decodes the wrong weight."""
 
     def __init__(self, in_features: int, out_features: int, w_bits: int, group_size: int,
                  bias: bool = False, scale_dtype: torch.dtype = torch.float16,
@@ -436,21 +501,33 @@ class QuantLinear(_PackedLinear):
                                                    device=device))
         self.register_buffer("g_idx", (torch.arange(in_features, dtype=torch.int32,
                                                     device=device) // g).to(torch.int32))
+        self.register_buffer("col_perm", None, persistent=False)
         self._register_extras(bias, bias_dtype, int(lowrank), lowrank_dtype, rotate_block, device)
 
     @classmethod
     def from_packed(cls, qweight: torch.Tensor, qzeros: torch.Tensor, scales: torch.Tensor,
                     w_bits: int, group_size: int, bias: Optional[torch.Tensor] = None,
                     g_idx: Optional[torch.Tensor] = None, device=None,
-                    lowrank=None, rotation=None, act_format=None) -> "QuantLinear":
+                    lowrank=None, rotation=None, act_format=None,
+                    act_order: bool = False) -> "QuantLinear":
         """From the packed tensors (a checkpoint's, or ``pack_quantized``'s).
-        `g_idx`, when given, must be the trivial ``arange(in) // group``.
+        `g_idx`, when given, must be the trivial ``arange(in) // group``, unless
+        ``act_order=True``: then any map with `group_size` columns in every group
+        is taken, `qweight` is sorted by group once, on the module's device (a
+        GPU), and the forward gathers x through ``col_perm``; a trivial map still
+        gives the static module.  ``act_format`` does not go with such a map.
         ``lowrank=(A, B)``: the correction's factors, (out, r) and (r, in).
         ``rotation=(block, sign_bits)``: the packed weight is that of the rotated
         basis and the forward rotates x first.  ``act_format``: None or "int8"."""
         m, n, g = _shapes(qweight, qzeros, scales, w_bits, group_size)
         extras = cls._extras_args(m, n, bias, lowrank, rotation)
-        if g_idx is not None:
+        col_perm = None
+        if g_idx is not None and act_order:
+            col_perm = _gidx_plan(g_idx, n, g)
+            if col_perm is not None and act_format is not None:
+                raise ValueError(f"act_format={act_format!r} cannot be combined with an act-order "
+                                 "g_idx (the INT8 kernel sums groups of consecutive columns)")
+        elif g_idx is not None:
             triv = torch.arange(n, dtype=torch.int64) // g
             if tuple(g_idx.shape) != (n,) or not torch.equal(g_idx.cpu().to(torch.int64), triv):
                 raise ValueError("g_idx is not the static arange(in_features) // group_size map "
@@ -458,22 +535,42 @@ class QuantLinear(_PackedLinear):
         dev = device if device is not None else qweight.device
         q = cls(n, m, w_bits, group_size, scale_dtype=scales.dtype, device=dev,
                 act_format=act_format, **extras)
+        if col_perm is not None:
+            q.col_perm = col_perm.to(dev)
+            qweight = _repack_gidx(qweight.to(dev), q.col_perm, w_bits)
+            q.g_idx.copy_(g_idx)
         return q._fill(dict(qweight=qweight, qzeros=qzeros, scales=scales), bias, lowrank, rotation)
 
     def extra_repr(self) -> str:
         act = f", act_format={self.act_format}" if self.act_format is not None else ""
+        act += ", act_order=True" if self.col_perm is not None else ""
         return (f"in_features={self.in_features}, out_features={self.out_features}, "
                 f"bits={self.w_bits}, group_size={self.group_size}, "
                 f"bias={self.bias is not None}{self._extras_repr()}{act}")
 
     def _dense(self, dtype: torch.dtype) -> torch.Tensor:
+        if self.col_perm is not None:
+            if dtype not in (torch.float16, torch.bfloat16, torch.float32):
+                raise ValueError(f"dtype must be float16, bfloat16 or float32, got {dtype}")
+            require_cuda(self.qweight, "QuantLinear.qweight")
+            n, m = self.in_features, self.out_features
+            return _dequant_gidx(self.qweight, self.qzeros, self.scales, self.col_perm, m, n,
+                                 self.group_size if self.group_size > 0 else n, self.w_bits, dtype)
         return dequantize_packed(self.qweight, self.qzeros, self.scales, self.w_bits,
                                  self.group_size, dtype)
 
     def _gemm(self, x2: torch.Tensor, T: int, ldx: int, bias: Optional[torch.Tensor],
               out: torch.Tensor) -> None:
         n, m = self.in_features, self.out_features
-        if self.act_format is not None:
+        if self.col_perm is not None:
+            nbytes = lib.tg_qgemm_gidx_workspace_size(T, m, n)
+            ws = workspace(nbytes, x2.device)
+            call("tg_qgemm_gidx", stream(), ptr(x2), DTYPES[x2.dtype], T, ldx,
+                 ptr(self.qweight), ptr(self.qzeros), ptr(self.scales),
+                 DTYPES[self.scales.dtype], m, n, self.group_size, self.w_bits, ptr(bias),
+                 DTYPES[bias.dtype] if bias is not None else 0, ptr(out), DTYPES[out.dtype], m,
+                 ptr(ws), nbytes, ptr(self.col_perm))
+        elif self.act_format is not None:
             nbytes = lib.tg_qgemm_act_workspace_size(T, m, n, self.group_size)
             ws = workspace(nbytes, x2.device)
             call("tg_qgemm_act", stream(), ptr(x2), DTYPES[x2.dtype], T, ldx,

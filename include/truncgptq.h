@@ -773,6 +773,52 @@ int tg_qgemm_act(void *stream, const void *X, int x_dtype, int T, int64_t stride
                  const void *bias, int bias_dtype, void *Y, int y_dtype, int64_t stride_y,
                  void *ws, size_t ws_bytes);
 
+/* ---- A21: act-order checkpoints (new; AutoGPTQ desc_act = true) -------------
+ * The A14 image with groups taken along a permutation of the input columns:
+ * g_idx[c] is the group of column c, every group has exactly g columns, and
+ * w[r, c] = (code_u[r, c] - zero_u[g_idx[c], r]) * scale[g_idx[c], r].  The host
+ * computes col_perm = argsort(g_idx, stable) (int32, n, a permutation of
+ * [0, n): the columns of group 0 ascending, then group 1, ...); the stream is
+ * sorted by it once, after which position j lies in group j / g and qzeros and
+ * scales are read as the static kernels read them.  Every kernel below reads a
+ * col_perm entry outside [0, n) as column 0 (wrong numbers, never an access
+ * outside the buffers).  n % 32 == 0 throughout; b in {2, 3, 4, 8}.
+ *
+ * tg_repack_gidx: out (n*b/32 x m int32, not aliasing qweight): position j of
+ * the bit stream of feature r holds the code of column col_perm[j] of qweight.
+ *
+ * tg_gather_cols: Y[t, j] = X[t, col_perm[j]], X (T x n, row stride stride_x
+ * >= n) and Y (T x n, row stride stride_y >= n, not aliasing X) of x_dtype
+ * TG_F16 / TG_BF16; the scattered reads happen in LDS.
+ *
+ * tg_qgemm_gidx: tg_qgemm's arguments, col_perm last; qweight is the sorted
+ * stream.  Y = X[:, col_perm] * W_sorted^T (+ bias) = X * W^T (+ bias), and bit
+ * for bit what tg_qgemm returns for the sorted stream and X[:, col_perm],
+ * under every setting of TG_QGEMM: where tg_qgemm takes its gemv regime the
+ * gather is fused into that kernel's staging of X (no extra launch, no copy);
+ * in the mfma regime one tg_gather_cols writes the sorted X into the workspace
+ * and tg_qgemm runs on it.  Same requirements and argument errors as tg_qgemm;
+ * ws is never null.
+ * tg_qgemm_gidx_workspace_size(T, m, n): T*n*2 bytes for the sorted X plus
+ * tg_qgemm_workspace_size(T, m, n) (+ alignment slack).
+ *
+ * tg_dequant_gidx: tg_dequant_packed's arguments, col_perm last; decodes the
+ * sorted stream and writes out[r, col_perm[j]], the dense weight in the
+ * original column order, with tg_dequant_packed's numerics. */
+int tg_repack_gidx(void *stream, const int32_t *qweight, const int32_t *col_perm, int m, int n,
+                   int w_bits, int32_t *out);
+int tg_gather_cols(void *stream, const void *X, int x_dtype, int T, int64_t stride_x, int n,
+                   const int32_t *col_perm, void *Y, int64_t stride_y);
+size_t tg_qgemm_gidx_workspace_size(int T, int m, int n);
+int tg_qgemm_gidx(void *stream, const void *X, int x_dtype, int T, int64_t stride_x,
+                  const int32_t *qweight, const int32_t *qzeros, const void *scales,
+                  int scale_dtype, int m, int n, int group, int w_bits, const void *bias,
+                  int bias_dtype, void *Y, int y_dtype, int64_t stride_y, void *ws, size_t ws_bytes,
+                  const int32_t *col_perm);
+int tg_dequant_gidx(void *stream, const int32_t *qweight, const int32_t *qzeros,
+                    const void *scales, int scale_dtype, int m, int n, int group, int w_bits,
+                    void *out, int out_dtype, int64_t stride_o, const int32_t *col_perm);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,7 +27,12 @@ adds tg_qgemm_mx and tg_qgemm of another build of the library, alternating too.
 beside the weights-only tg_qgemm and the dense fp16 matmul, alternating inside
 every run, at m x n = 4096 x 4096 and 14336 x 4096; the sweep is taken twice.
 
+--act-order (integer format) times tg_qgemm_gidx on a random-permutation g_idx
+beside the static tg_qgemm on the same packed words and beside tg_gather_cols +
+tg_qgemm, alternating inside every run, at 4096 x 4096, and tg_repack_gidx alone.
+
     python tools/qgemm_bench.py --act int8 --T 1 16 64 512 4096 --out profiles/qlinear/qiact.json
+    python tools/qgemm_bench.py --act-order --T 1 16 512 --out profiles/qlinear/qgidx.json
     python tools/qgemm_bench.py [--graph] [--format int|mxfp4] [--group G] [--out FILE]
     python tools/qgemm_bench.py --format mxfp4 --act mxfp8 [--other-lib SO] [--out FILE]
 """
@@ -272,6 +277,87 @@ def main_iact(args):
     print("wrote", args.out)
 
 
+def main_gidx(args):
+    """--act-order (integer format, 4-bit, --group, m = n = 4096): tg_qgemm_gidx
+    with a random-permutation g_idx beside the static tg_qgemm on the same packed
+    tensors (a sorted stream is a stream like any other, so both read the same
+    words) and beside a separate tg_gather_cols launch followed by the static
+    call, alternating inside every run; and the one-off tg_repack_gidx alone.
+    --other-lib adds the static tg_qgemm of another build of the library."""
+    other = bind_other(args.other_lib) if args.other_lib else None
+    gen = torch.Generator().manual_seed(0)
+    flush = torch.empty(1 << 30, dtype=torch.uint8, device=DEV)
+    m = n = 4096
+    g_idx = torch.empty(n, dtype=torch.int64)
+    g_idx[torch.randperm(n, generator=gen)] = torch.arange(n) // GROUP
+    cp = torch.argsort(g_idx, stable=True).to(torch.int32).to(DEV)
+    qw, qz, sc = random_packed(m, n, gen, "int")
+    packed_bytes = qw.numel() * 4 + qz.numel() * 4 + sc.numel() * 2
+    pc = -(-ROTATE_BYTES // packed_bytes)
+    packs = [(qw, qz, sc)] + [(qw.clone(), qz.clone(), sc.clone()) for _ in range(pc - 1)]
+    out = torch.empty_like(qw)
+    repack = timed_alternating(
+        {"repack": (lambda i: L.call("tg_repack_gidx", L.stream(), L.ptr(packs[i][0]), L.ptr(cp), m,
+                                     n, BITS, L.ptr(out)), pc)}, flush, args.warmup, args.runs)
+    rows = []
+    for T in args.T:
+        x = torch.randn(T, n, generator=gen).to(torch.float16).to(DEV)
+        xg = torch.empty_like(x)
+        y = torch.empty(T, m, dtype=torch.float16, device=DEV)
+        nb_s = L.lib.tg_qgemm_workspace_size(T, m, n)
+        nb_a = L.lib.tg_qgemm_gidx_workspace_size(T, m, n)
+        ws_s, ws_a = L.workspace(nb_s, DEV), L.workspace(nb_a, DEV)
+
+        def static(i, xin=None):
+            a, b, c = packs[i]
+            L.call("tg_qgemm", L.stream(), L.ptr(x if xin is None else xin), L.TG_F16, T, n,
+                   L.ptr(a), L.ptr(b), L.ptr(c), L.TG_F16, m, n, GROUP, BITS, None, 0, L.ptr(y),
+                   L.TG_F16, m, L.ptr(ws_s), nb_s)
+
+        def act_order(i):
+            a, b, c = packs[i]
+            L.call("tg_qgemm_gidx", L.stream(), L.ptr(x), L.TG_F16, T, n, L.ptr(a), L.ptr(b),
+                   L.ptr(c), L.TG_F16, m, n, GROUP, BITS, None, 0, L.ptr(y), L.TG_F16, m,
+                   L.ptr(ws_a), nb_a, L.ptr(cp))
+
+        def gather_static(i):
+            L.call("tg_gather_cols", L.stream(), L.ptr(x), L.TG_F16, T, n, n, L.ptr(cp), L.ptr(xg), n)
+            static(i, xg)
+
+        def static_other(i):
+            a, b, c = packs[i]
+            other.tg_qgemm(L.stream(), L.ptr(x), L.TG_F16, T, n, L.ptr(a), L.ptr(b), L.ptr(c),
+                           L.TG_F16, m, n, GROUP, BITS, None, 0, L.ptr(y), L.TG_F16, m,
+                           L.ptr(ws_s), nb_s)
+
+        paths = {"act_order": (act_order, pc), "static": (static, pc),
+                 "gather_static": (gather_static, pc)}
+        if other is not None:
+            paths["static_other"] = (static_other, pc)
+        t = timed_alternating(paths, flush, args.warmup, args.runs)
+        act_order(0)
+        got = y.clone()
+        gather_static(0)
+        row = dict(m=m, n=n, T=T, packed_copies=pc, same_bits_as_gather_static=bool(torch.equal(got, y)),
+                   ratio_vs_static=t["act_order"][0] / t["static"][0])
+        for k, (med, mn) in t.items():
+            row[k + "_ms"], row[k + "_min_ms"] = med, mn
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    res = dict(device=torch.cuda.get_device_name(0), format="int", bits=BITS, group=GROUP,
+               act_order=True, dtype="float16", runs=args.runs, warmup=args.warmup, launch="eager",
+               regime=os.environ.get("TG_QGEMM", "auto"),
+               repack_ms=repack["repack"][0], repack_min_ms=repack["repack"][1],
+               method="HIP events around one call on each of >= 768 MB of weight copies, "
+                      "per-call median; 1 GiB overwritten before every bracket; the paths "
+                      "alternate inside every run", rows=rows)
+    print(json.dumps({k: v for k, v in res.items() if k != "rows"}), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+    print("wrote", args.out)
+
+
 def main():
     global GROUP
     ap = argparse.ArgumentParser()
@@ -286,8 +372,12 @@ def main():
     ap.add_argument("--act", choices=["mxfp8", "int8"], default=None,
                     help="mxfp8 (with --format mxfp4): time tg_qgemm_mx_act beside the other "
                          "paths; int8 (integer format): tg_qgemm_act likewise")
+    ap.add_argument("--act-order", action="store_true",
+                    help="integer format: time tg_qgemm_gidx on a random-permutation g_idx beside "
+                         "the static tg_qgemm of the same shape (4096 x 4096)")
     ap.add_argument("--other-lib", default=None,
-                    help="with --act: another build of libtruncgptq.so to time against")
+                    help="with --act or --act-order: another build of libtruncgptq.so to time "
+                         "against")
     args = ap.parse_args()
     mx = args.format == "mxfp4"
     GROUP = 32 if mx else args.group
@@ -295,6 +385,10 @@ def main():
         raise SystemExit("--act mxfp8 needs --format mxfp4, --act int8 the integer format")
     if not torch.cuda.is_available():
         raise SystemExit("qgemm_bench needs the GPU (there is nothing to time without one)")
+    if args.act_order:
+        if mx or args.act:
+            raise SystemExit("--act-order needs the integer format and no --act")
+        return main_gidx(args)
     if args.act == "int8":
         return main_iact(args)
     if args.act:
