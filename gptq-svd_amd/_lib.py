@@ -120,6 +120,9 @@ _SIGS = {
     "tg_qgemm_gidx": ([_vp, _vp, _i, _i, _i64, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _i,
                        _i64, _vp, _sz, _vp], _i),
     "tg_dequant_gidx": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _i64, _vp], _i),
+    "tg_qgemm_grouped_act_workspace_size": ([_i, _i, _i, _i, _i], _sz),
+    "tg_qgemm_grouped_act": ([_vp, _vp, _i, _i, _i64, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i,
+                              _vp, _vp, _i, _i64, _vp, _sz], _i),
 }
 
 EXPORTED = []

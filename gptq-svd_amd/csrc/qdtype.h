@@ -1,8 +1,8 @@
 // Shared by the packed-inference files (qlinear.hip, qmxact.hip, qiact.hip,
-// qgrouped.hip, lrinfer.hip): the 16-bit operand / output types as raw bits,
-// and the split-K reduction that finishes the partial sums of qlinear.hip,
-// qmxact.hip and lrinfer.hip (bias only; qgrouped.hip and qiact.hip, which
-// scale the rows, have their own).
+// qgrouped.hip, qgroupedact.hip, lrinfer.hip): the 16-bit operand / output types
+// as raw bits, and the split-K reduction that finishes the partial sums of
+// qlinear.hip, qmxact.hip and lrinfer.hip (bias only; the grouped files and
+// qiact.hip, which scale the rows, have their own: qgrouped_work.h, qiact.hip).
 #pragma once
 #include <hip/hip_bf16.h>
 #include <hip/hip_fp16.h>

@@ -211,9 +211,10 @@ def _rotation_of(tensors: Dict[str, torch.Tensor], name: str, blocks: Dict[str, 
 
 
 def _load_experts(model: torch.nn.Module, tensors: Dict[str, torch.Tensor], qc: Dict[str, Any],
-                  used: set) -> None:
+                  used: set, act_format=None) -> None:
     """Every module listed under ``"experts"`` becomes a ``qlinear.QuantExperts``
-    holding its two packed stacks; `used` gains the tensors taken."""
+    holding its two packed stacks, with `act_format` as its activation format;
+    `used` gains the tensors taken."""
     from .qlinear import QuantExperts
     mx = qc.get("checkpoint_format") == "mxfp4"
     for name in qc.get("experts", []):
@@ -237,7 +238,7 @@ def _load_experts(model: torch.nn.Module, tensors: Dict[str, torch.Tensor], qc: 
             q = QuantExperts.from_packed(stacks[0], stacks[1], int(qc["bits"]),
                                          int(qc["group_size"]), "mxfp4" if mx else "int",
                                          act_fn=getattr(mod, "act_fn", None),
-                                         device=mod.gate_up_proj.device)
+                                         device=mod.gate_up_proj.device, act_format=act_format)
         except ValueError as e:
             raise ValueError(f"{name}: {e}") from None
         if (q.num_experts, 2 * q.intermediate_dim, q.hidden_dim) != tuple(mod.gate_up_proj.shape):
@@ -261,7 +262,8 @@ def _set_submodule(model: torch.nn.Module, name: str, new: torch.nn.Module) -> N
 
 
 def load_quantized(model: torch.nn.Module, path: str, device=None,
-                   act_format=None, act_order: bool = False) -> torch.nn.Module:
+                   act_format=None, act_order: bool = False,
+                   experts_act_format=None) -> torch.nn.Module:
     """Load a checkpoint written by save_quantized into `model` (the dense
     architecture, any weights) and return it: every ``nn.Linear`` whose
     ``<name>.qweight`` is in the checkpoint becomes a ``qlinear.QuantLinear``
@@ -287,8 +289,21 @@ def load_quantized(model: torch.nn.Module, path: str, device=None,
     (``QuantLinear.from_packed(..., act_order=True)``).  The sort is a kernel, so
     such a layer is built on `device` when that is given and on the model's device
     otherwise, and one of them must be a GPU.  MXFP4 and experts checkpoints have
-    no ``g_idx``; nothing changes for them."""
-    from .qlinear import ACT_FORMATS, INT_ACT_FORMATS, MXQuantLinear, QuantLinear
+    no ``g_idx``; nothing changes for them.
+    `experts_act_format`: the same run-time choice for the ``QuantExperts`` modules
+    alone (the packed linears keep `act_format`).  None: 16-bit activations.
+    "mxfp8": both grouped GEMMs of every experts module run on the block-scaled
+    MFMA, for MXFP4 checkpoints only; anything else, and "mxfp8" with an integer
+    checkpoint, are a ``ValueError`` before any tensor is read."""
+    from .qlinear import (ACT_FORMATS, INT_ACT_FORMATS, MXQuantLinear, QuantLinear,
+                          _check_act_format)
+    if experts_act_format is not None:           # before any tensor is read
+        _check_act_format(experts_act_format, ACT_FORMATS, " for experts_act_format")
+        with open(os.path.join(path, "quantize_config.json")) as f:
+            fmt = json.load(f).get("checkpoint_format", "gptq_v2")
+        if fmt != "mxfp4":
+            raise ValueError(f"experts_act_format={experts_act_format!r} needs an mxfp4 "
+                             f"checkpoint; this one is {fmt!r}")
     if act_format is not None:                   # before any tensor is read
         known = sorted(ACT_FORMATS) + sorted(INT_ACT_FORMATS)
         if not isinstance(act_format, str) or act_format not in known:
@@ -343,7 +358,7 @@ def load_quantized(model: torch.nn.Module, path: str, device=None,
                                            device=dev, lowrank=lowrank, rotation=rotation,
                                            act_format=act_format, act_order=act_order)
     used = set()
-    _load_experts(model, tensors, qc, used)
+    _load_experts(model, tensors, qc, used, experts_act_format)
     _load_linears(model, tensors, used, blocks, required, build)
     return _load_rest(model, tensors, used, device)
 

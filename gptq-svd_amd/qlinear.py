@@ -738,14 +738,20 @@ class MXQuantLinear(_PackedLinear):
 def qgemm_grouped(x: torch.Tensor, rows: Optional[torch.Tensor], offsets: torch.Tensor,
                   qweight: torch.Tensor, qzeros: Optional[torch.Tensor], scales: torch.Tensor,
                   w_bits: int, group_size: int, row_scale: Optional[torch.Tensor] = None,
-                  dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+                  dtype: Optional[torch.dtype] = None, act_format=None) -> torch.Tensor:
     """``Y[i] = row_scale[i] * x[rows[i]] @ W^_e^T`` for every slot i of expert e,
     ``offsets[e] <= i < offsets[e + 1]`` (``tg_qgemm_grouped``).  x (T, n) fp16 /
     bf16; rows int32 (R,) or None (slot i reads row i); offsets int32 (E + 1,);
     qweight (E, n*b/32, m) with qzeros (E, G, m*b/32) and scales (E, G, m), or
     ``qzeros=None`` with uint8 scales (E, n/32, m) for MXFP4; row_scale fp32 (R,)
     or None.  Returns (R, m) of `dtype` (x's, or float32).  Everything stays on
-    the device: nothing is read back."""
+    the device: nothing is read back.  ``act_format="mxfp8"`` (MXFP4 stacks only):
+    every row of x is quantised to MXFP8 once and both operands go to the
+    block-scaled MFMA as they lie in memory (``tg_qgemm_grouped_act``)."""
+    _check_act_format(act_format, ACT_FORMATS, " for qgemm_grouped")
+    if act_format is not None and qzeros is not None:
+        raise ValueError(f"qgemm_grouped: act_format={act_format!r} needs MXFP4 stacks "
+                         "(qzeros=None, uint8 scales); integer stacks take 16-bit activations")
     require_cuda(x, "qgemm_grouped input")
     if x.dtype not in (torch.float16, torch.bfloat16):
         raise RuntimeError(f"qgemm_grouped takes float16 or bfloat16 activations, got {x.dtype} "
@@ -769,6 +775,14 @@ def qgemm_grouped(x: torch.Tensor, rows: Optional[torch.Tensor], offsets: torch.
         return y
     x, T, ldx = _rows(x, n)
     with torch.cuda.device(x.device):
+        if act_format is not None:
+            nbytes = lib.tg_qgemm_grouped_act_workspace_size(T, R, E, m, n)
+            ws = workspace(nbytes, x.device)
+            call("tg_qgemm_grouped_act", stream(), ptr(x), DTYPES[x.dtype], T, ldx, ptr(rows),
+                 ptr(offsets), R, E, ptr(qweight), ptr(scales), TG_FMT_MXFP4,
+                 ACT_FORMATS[act_format], m, n, ptr(row_scale), ptr(y), DTYPES[dtype], m, ptr(ws),
+                 nbytes)
+            return y
         nbytes = lib.tg_qgemm_grouped_workspace_size(R, E, m, n)
         ws = workspace(nbytes, x.device)
         call("tg_qgemm_grouped", stream(), ptr(x), DTYPES[x.dtype], T, ldx, ptr(rows), ptr(offsets),
@@ -786,14 +800,24 @@ class QuantExperts(nn.Module):
     (E, G, 2I*b/32), ``gate_up_scales`` (E, G, 2I) and the same three for ``down``
     with H and I exchanged; every ``[e]`` is what ``pack_quantized`` returns for
     that expert.  ``weight_format="mxfp4"``: no ``qzeros``, uint8 ``scales``
-    (E, in/32, out), bits 4 and group 32.  There is no bias."""
+    (E, in/32, out), bits 4 and group 32.  There is no bias.
+    ``act_format`` (a plain attribute, not in the ``state_dict``): None, 16-bit
+    activations; "mxfp8", for ``weight_format="mxfp4"``: both grouped calls
+    quantise their input to MXFP8 and run on the block-scaled MFMA
+    (``qgemm_grouped(act_format="mxfp8")``); the SwiGLU between them stays 16-bit."""
 
     def __init__(self, num_experts: int, hidden_dim: int, intermediate_dim: int, w_bits: int = 4,
                  group_size: int = -1, weight_format: str = "int",
-                 scale_dtype: torch.dtype = torch.float16, act_fn=None, device=None):
+                 scale_dtype: torch.dtype = torch.float16, act_fn=None, device=None,
+                 act_format=None):
         super().__init__()
         if weight_format not in ("int", "mxfp4"):
             raise ValueError(f"weight_format must be 'int' or 'mxfp4', got {weight_format!r}")
+        _check_act_format(act_format, ACT_FORMATS, " for QuantExperts")
+        if act_format is not None and weight_format != "mxfp4":
+            raise ValueError(f"act_format={act_format!r} needs weight_format='mxfp4', got "
+                             f"{weight_format!r}")
+        self.act_format = act_format
         mx = weight_format == "mxfp4"
         if mx:
             w_bits, group_size = 4, 32
@@ -828,7 +852,8 @@ class QuantExperts(nn.Module):
 
     @classmethod
     def from_packed(cls, gate_up: dict, down: dict, w_bits: int = 4, group_size: int = -1,
-                    weight_format: str = "int", act_fn=None, device=None) -> "QuantExperts":
+                    weight_format: str = "int", act_fn=None, device=None,
+                    act_format=None) -> "QuantExperts":
         """From the two stacked entries (a checkpoint's, or ``quantize_model``'s
         ``packed``): dicts of ``qweight`` (E, in*b/32, out), ``qzeros`` (None for
         MXFP4) and ``scales``."""
@@ -838,7 +863,8 @@ class QuantExperts(nn.Module):
         H, I = nw * 32 // w_bits, m2 // 2
         dev = device if device is not None else gate_up["qweight"].device
         q = cls(E, H, I, w_bits, group_size, weight_format, scale_dtype=gate_up["scales"].dtype
-                if weight_format == "int" else torch.float16, act_fn=act_fn, device=dev)
+                if weight_format == "int" else torch.float16, act_fn=act_fn, device=dev,
+                act_format=act_format)
         for name, t in (("gate_up", gate_up), ("down", down)):
             for k in ("qweight", "qzeros", "scales"):
                 buf = getattr(q, f"{name}_{k}")
@@ -854,8 +880,9 @@ class QuantExperts(nn.Module):
     def extra_repr(self) -> str:
         fmt = "format=mxfp4" if self.weight_format == "mxfp4" else \
             f"bits={self.w_bits}, group_size={self.group_size}"
+        act = f", act_format={self.act_format}" if self.act_format is not None else ""
         return (f"num_experts={self.num_experts}, hidden_dim={self.hidden_dim}, "
-                f"intermediate_dim={self.intermediate_dim}, {fmt}")
+                f"intermediate_dim={self.intermediate_dim}, {fmt}{act}")
 
     def dequantize(self, dtype: torch.dtype = torch.float16):
         """The dense ``(gate_up_proj (E, 2I, H), down_proj (E, H, I))`` of `dtype`."""
@@ -888,11 +915,13 @@ class QuantExperts(nn.Module):
         offsets = torch.searchsorted(flat[order], torch.arange(
             self.num_experts + 1, device=flat.device, dtype=flat.dtype)).to(torch.int32)
         gu = qgemm_grouped(x, rows, offsets, self.gate_up_qweight, self.gate_up_qzeros,
-                           self.gate_up_scales, self.w_bits, self.group_size)
+                           self.gate_up_scales, self.w_bits, self.group_size,
+                           act_format=self.act_format)
         h = self.act_fn(gu[:, :I]) * gu[:, I:]
         scale = top_k_weights.reshape(-1)[order].to(torch.float32)
         d = qgemm_grouped(h, None, offsets, self.down_qweight, self.down_qzeros, self.down_scales,
-                          self.w_bits, self.group_size, row_scale=scale)
+                          self.w_bits, self.group_size, row_scale=scale,
+                          act_format=self.act_format)
         # token t's k slots through the inverse permutation, added in fp32 in choice
         # order and rounded once (index_add_ would use atomics)
         slot = torch.empty_like(order)

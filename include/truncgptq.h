@@ -819,6 +819,44 @@ int tg_dequant_gidx(void *stream, const int32_t *qweight, const int32_t *qzeros,
                     const void *scales, int scale_dtype, int m, int n, int group, int w_bits,
                     void *out, int out_dtype, int64_t stride_o, const int32_t *col_perm);
 
+/* ---- A22: grouped packed GEMM with MXFP8 activations (new; opt-in W4A8 for the
+ * experts of an MXFP4 Mixture-of-Experts checkpoint) ----------------------------
+ * tg_qgemm_grouped's contract (A19: slots, offsets, rows, row_scale, clamping of
+ * malformed routing, no host read of the routing) on tg_qgemm_mx_act's operands:
+ *   Y[i, r] = round(row_scale[i] * sum_k X^[rows[i], k] * W^_e[r, k]),  r < m,
+ * for every slot i of expert e, offsets[e] <= i < offsets[e + 1].  X^ is exactly
+ * tg_quant_act_mx's output for the T rows of X, decoded; W^_e is exactly
+ * tg_dequant_mx's TG_F32 output of expert e's pair, qweight (E x n/8 x m) and
+ * scales_e8m0 (E x n/32 x m).  wfmt must be TG_FMT_MXFP4 and act_fmt
+ * TG_ACT_MXFP8.  Both operands go to v_mfma_scale_f32_16x16x128_f8f6f4 as they
+ * lie in memory.  Accumulation is f32 (inside a 128-value step in the
+ * instruction's order, across steps in ascending k; at 16 slots per workgroup
+ * the even and the odd steps of a split are summed apart and added at its end);
+ * row_scale is multiplied in f32 after the sum; one rounding to y_dtype (x_dtype
+ * or TG_F32).  No atomics: bit-identical from call to call.  A slot whose rows
+ * entry lies outside [0, T) reads zeros.
+ * One regime for every R: every row of X is quantised once, row-major, into the
+ * workspace (a token that feeds k slots is quantised once, not k times); a
+ * workgroup owns 16 slots (R <= 32 E: the average run is at most 32) or 64 slots
+ * of one expert x 64 features and walks K in steps of 128, gathering its rows of
+ * X^ through `rows`.  While the bound on the tiles, (R + E (BM - 1)) / BM
+ * feature-tile columns, is below ~512 workgroups K is split into S parts of at
+ * least 4 steps; the partial sums [S][R][m] f32 go to the workspace and a second
+ * kernel adds them in ascending split order, applies row_scale and rounds.
+ * TG_QGROUPED_ACT = 16 | 64 (read per call, by the size function too) forces
+ * the tile height.
+ * Requires n % 32 == 0, (m * 4) % 32 == 0, 1 <= E <= 256, R >= 0; R = 0 returns
+ * 0 at once; anything else is rejected with the argument's index before any
+ * device work.
+ * tg_qgemm_grouped_act_workspace_size(T, R, E, m, n): T*n + T*n/32 bytes of X^,
+ * plus S*R*m*4 bytes when S > 1, plus alignment slack; ws is never null. */
+size_t tg_qgemm_grouped_act_workspace_size(int T, int R, int E, int m, int n);
+int tg_qgemm_grouped_act(void *stream, const void *X, int x_dtype, int T, int64_t stride_x,
+                         const int32_t *rows, const int32_t *offsets, int R, int E,
+                         const int32_t *qweight, const uint8_t *scales_e8m0, int wfmt, int act_fmt,
+                         int m, int n, const float *row_scale, void *Y, int y_dtype,
+                         int64_t stride_y, void *ws, size_t ws_bytes);
+
 #ifdef __cplusplus
 }
 #endif

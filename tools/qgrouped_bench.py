@@ -19,7 +19,14 @@ HIP-event bracket each around one forward on each of the weight copies (packed:
 before every bracket), per-forward median over --runs brackets.  The whole
 measurement is made twice; both medians and their spread are reported.
 
-    python tools/qgrouped_bench.py [--T 1 16 2048] [--out FILE]
+--act mxfp8 times the MXFP8-activation path instead: the bare pair of
+tg_qgemm_grouped_act calls (the activation quantiser inside each) against the
+bare pair of tg_qgemm_grouped calls at its production dispatch, MXFP4 experts,
+same routing, same method (graph replay over the three weight copies, paths
+alternating); act_auto is the production tile height, act_16 / act_64 force one
+(TG_QGROUPED_ACT).  Neither the dense module nor the loop is built in this mode.
+
+    python tools/qgrouped_bench.py [--T 1 16 2048] [--act mxfp8] [--out FILE]
 """
 import argparse
 import json
@@ -87,12 +94,14 @@ def loop_forward(q, x, idx, w):
     return out
 
 
-def bare_pairs(packs, x, idx, w, regimes, warmup):
+def bare_pairs(packs, x, idx, w, regimes, warmup, env="TG_QGROUPED", prefix="pair_",
+               act_format=None):
     """{pair_<regime>: (replay, copies)}: the gate_up and down calls alone, on
     routing sorted beforehand, on each weight copy, captured once per regime
     (TG_QGROUPED is read when the call is made, i.e. at capture) and replayed, so
     neither torch's launches around the calls nor the host's launch cost is in
-    the bracket.  This is what the `auto` boundary is read from."""
+    the bracket.  This is what the `auto` boundary is read from.  With act_format
+    the same pair through tg_qgemm_grouped_act, `regimes` being values of `env`."""
     flat = idx.reshape(-1)
     order = torch.argsort(flat, stable=True)
     rows = (order // K).to(torch.int32)
@@ -101,14 +110,14 @@ def bare_pairs(packs, x, idx, w, regimes, warmup):
     h = torch.randn(order.numel(), I, device=DEV).half()
     paths = {}
     for regime in regimes:
-        os.environ["TG_QGROUPED"] = regime
+        os.environ[env] = regime
 
         def sweep():
             for q in packs:
                 qgemm_grouped(x, rows, off, q.gate_up_qweight, q.gate_up_qzeros, q.gate_up_scales,
-                              BITS, q.group_size)
+                              BITS, q.group_size, act_format=act_format)
                 qgemm_grouped(h, None, off, q.down_qweight, q.down_qzeros, q.down_scales, BITS,
-                              q.group_size, row_scale=scale)
+                              q.group_size, row_scale=scale, act_format=act_format)
         for _ in range(warmup):
             sweep()
         torch.cuda.synchronize()
@@ -116,8 +125,38 @@ def bare_pairs(packs, x, idx, w, regimes, warmup):
         with torch.cuda.graph(g):
             sweep()
         # one replay covers every copy
-        paths["pair_" + regime] = (lambda i, g=g: g.replay() if i == 0 else None, len(packs))
+        paths[prefix + regime] = (lambda i, g=g: g.replay() if i == 0 else None, len(packs))
     return paths
+
+
+def act_rows(args, gen, flush):
+    """--act: one row per T, MXFP4 experts, the two bare pairs side by side."""
+    packs = [random_experts(gen, "mxfp4") for _ in range(3)]
+    rows = []
+    for T in args.T:
+        x = torch.randn(T, H, generator=gen).half().to(DEV)
+        idx = torch.stack([torch.randperm(E, generator=gen)[:K] for _ in range(T)]).to(DEV)
+        w = torch.softmax(torch.randn(T, K, generator=gen), dim=-1).half().to(DEV)
+        with torch.no_grad():
+            paths = bare_pairs(packs, x, idx, w, ["auto"], args.warmup)
+            paths.update(bare_pairs(packs, x, idx, w, ["auto", "16", "64"], args.warmup,
+                                    env="TG_QGROUPED_ACT", prefix="act_", act_format=args.act))
+            os.environ["TG_QGROUPED_ACT"] = "auto"
+            two = [measure(paths, flush, args.warmup, args.runs) for _ in range(2)]
+            ref = packs[0](x, idx, w).float()
+            packs[0].act_format = args.act
+            rel = float((packs[0](x, idx, w).float() - ref).abs().max() / ref.abs().max())
+            packs[0].act_format = None
+        row = dict(format="mxfp4", act=args.act, T=T, R=T * K, max_rel_diff_vs_16bit=rel)
+        for k in paths:
+            a, b = two[0][k], two[1][k]
+            row[k + "_ms"] = [a, b]
+            row[k + "_spread"] = abs(a - b) / min(a, b)
+        row["w16_over_act"] = min(two[0]["pair_auto"], two[1]["pair_auto"]) / \
+            max(two[0]["act_auto"], two[1]["act_auto"])
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    return rows
 
 
 def measure(paths, flush, warmup, runs):
@@ -148,6 +187,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--T", type=int, nargs="+", default=[1, 16, 2048])
     ap.add_argument("--formats", nargs="+", default=["int", "mxfp4"])
+    ap.add_argument("--act", choices=["mxfp8"], default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("qgrouped_bench needs the GPU (there is nothing to time without one)")
@@ -157,8 +197,8 @@ def main():
     flush = torch.empty(1 << 30, dtype=torch.uint8, device=DEV)
     cfg = Qwen3MoeConfig(hidden_size=H, moe_intermediate_size=I, num_experts=E,
                          num_experts_per_tok=K)
-    rows = []
-    for fmt in args.formats:
+    rows = act_rows(args, gen, flush) if args.act else []
+    for fmt in ([] if args.act else args.formats):
         packs = [random_experts(gen, fmt) for _ in range(3)]
         denses = []
         for q in packs[:2]:
